@@ -11,7 +11,16 @@ weights. W untimed warm-up steps, then EXACTLY K timed steps bracketed by a
 barrier + device synchronize on both sides; the MAX elapsed over ranks is used.
 Rank 0 prints ONE JSON line.
 
-Self-validation for N > 1 (everything below runs AFTER the timed region):
+A plain run does only that: set up, warm up, time the K steps, write the outputs when
+``--dump-outputs DIR`` is given, print the record. ``--dump-outputs DIR`` stores what the last timed
+step left its caller -- the loss, the updated weights, momentum and BatchNorm running statistics --
+as ``DIR/<name>.npy`` (float32; a fixed seeded sample of an array above 4 Mi elements, so two builds
+run with the same arguments can be compared array for array: weights and batches are seeded).
+Everything else described below is measured or checked only with ``--full``, after the timed
+region: the device-busy %, the weight checksum, the fp32 / fp16-AMP / DataParallel passes and the
+N > 1 diagnostics.
+
+Self-validation for N > 1 (``--full``; everything below runs AFTER the timed region):
 
 * ``rccl_world``: the rank count RCCL itself reports for the gradient communicator
   (``ncclCommCount``), next to ``n_gpus`` from the launcher;
@@ -106,6 +115,13 @@ def parse():
                          "own tuning for the topology")
     ap.add_argument("--nccl-proto", default="", help="NCCL_PROTO (LL, LL128, Simple; '' = RCCL's choice)")
     ap.add_argument("--nccl-algo", default="", help="NCCL_ALGO (Ring, Tree; '' = RCCL's choice)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary measurement and check: "
+                         "device-busy %%, weight checksum, the fp32 / fp16-AMP / DataParallel passes, "
+                         "for N>1 the bucket timing, communicator probe and cross-rank consistency")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, updated weights, momentum, "
+                         "BatchNorm running statistics) to DIR/<name>.npy")
     ap.add_argument("--rehearse-fold", action="store_true",
                     help="allow more ranks than visible GPUs (several ranks share a device: launch "
                          "rehearsals only, never a measurement)")
@@ -500,7 +516,7 @@ def _dp_pass(ctx: Ctx, args, dtype) -> dict:
                    if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK",
                                 "ROLE_RANK", "ROLE_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
                    and not k.startswith("TORCHELASTIC")}
-            cmd = [sys.executable, os.path.abspath(__file__), "--dp", "--gpus", str(n),
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--dp", "--gpus", str(n),
                    "--steps", str(args.dp_steps), "--warmup", "3", "--batch", str(args.batch),
                    "--arch", args.arch, "--image-size", str(args.image_size), "--dtype", args.dtype,
                    "--fp32-steps", "0", "--amp-steps", "0", "--dp-steps", "0",
@@ -535,6 +551,43 @@ def _dp_pass(ctx: Ctx, args, dtype) -> dict:
         store.wait(["pda_bench_dp_done"], datetime.timedelta(seconds=limit + 120))
         res = json.loads(store.get("pda_bench_dp_done").decode())
     return res
+
+
+DUMP_SAMPLE = 4 << 20     # elements kept of a larger array: 4 arrays stay far below 64 MB in all
+
+
+def _dump_outputs(tr, loss, out_dir: str) -> None:
+    """``--dump-outputs``: the state the last timed step left its caller, as float32 ``.npy`` files:
+    ``loss`` (the step's loss), ``params`` (every parameter of the model, flattened in
+    ``model.parameters()`` order; the f32 master weights of the native engine), ``momentum`` (the
+    SGD momentum: the native engine's flat buffer, else the per-parameter buffers in the same
+    order) and ``buffers`` (the floating-point module buffers: BatchNorm running mean / variance).
+    An array above DUMP_SAMPLE elements is stored as the elements at DUMP_SAMPLE sorted indices
+    drawn once from a fixed seed, the same for every run with the same arguments."""
+    import numpy as np
+    model = getattr(tr, "model", None)
+    opt = tr.opt
+    if model is None:                      # DataParallel replicas: replica 0 (all are identical)
+        model, opt = tr.dp.all_modules[0], tr.opt.opts[0]
+    params = list(model.parameters())
+    if hasattr(opt, "flat_mom"):
+        moms = [opt.flat_mom]
+    else:
+        moms = [opt.state.get(p, {}).get("momentum_buffer") for p in params]
+    groups = {"loss": [] if loss is None else [torch.tensor([loss], dtype=torch.float32)],
+              "params": params,
+              "momentum": [m for m in moms if m is not None],
+              "buffers": [b for b in model.buffers() if b.is_floating_point()]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, ts in groups.items():
+        if not ts:
+            continue
+        with torch.no_grad():
+            flat = torch.cat([t.detach().float().reshape(-1) for t in ts])
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+                flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy().astype(np.float32))
 
 
 def main():
@@ -581,14 +634,16 @@ def main():
         tr.step(i)
     ctx.sync()
     util_devs = (list(range(args.gpus)) if args.dp else [ctx.device.index]) if ctx.cuda else []
-    with BusySampler(util_devs) as busy:
+    with BusySampler(util_devs if args.full else []) as busy:
         elapsed = _timed(ctx, tr, args.warmup, args.steps)   # barrier + sync on both sides, MAX
     loss = tr.last_loss()
+    if args.dump_outputs and ctx.rank == 0:
+        _dump_outputs(tr, loss, args.dump_outputs)   # before any further step moves the state
     nxt = args.warmup + args.steps
-    diag = _diagnostics(ctx, tr, nxt) if ctx.multi else {}
-    if ctx.multi:
+    diag = _diagnostics(ctx, tr, nxt) if ctx.multi and args.full else {}
+    if ctx.multi and args.full:
         diag.update(_comm_probe(ctx, tr))
-    if args.dp and getattr(tr.dp, "replicas", None):
+    if args.full and args.dp and getattr(tr.dp, "replicas", None):
         # one more (untimed) step with HIP events at the end of backward and after the last
         # gradient all-reduce (per-stage slices overlapped with the backward's later segments)
         tr.dp.timing = True
@@ -602,7 +657,7 @@ def main():
         diag["dp_segments"] = len(rg.graphs)
         diag["dp_side_graphs"] = sum(g is not None for g in getattr(rg, "sides", []))
         nxt += 1
-    if args.dp and not getattr(tr.dp, "replicas", None) and ctx.cuda and args.steps > 0:
+    if args.full and args.dp and not getattr(tr.dp, "replicas", None) and ctx.cuda and args.steps > 0:
         # one device: the eager step above is what torch's DataParallel does for one device; the
         # replica-graph replay an N > 1 run takes (per-block segment graphs + weight-gradient side
         # graphs) is timed here too, so that path has a number on every 1-GPU record
@@ -617,7 +672,9 @@ def main():
         diag["dp_replay_segments"] = len(tr.dp._graphs[0].graphs)
         diag["dp_side_graphs"] = sum(g is not None for g in getattr(tr.dp._graphs[0], "sides", []))
         tr.dp.force_replay = False
-    if args.dp:   # every replica must hold bit-identical weights (the replicated fused SGD)
+    if not args.full:
+        consistency = {}
+    elif args.dp:   # every replica must hold bit-identical weights (the replicated fused SGD)
         try:
             tr.state_checksum()
             consistency = {"replicas_consistent": True}
@@ -640,7 +697,7 @@ def main():
     max_mem = round(torch.cuda.max_memory_allocated(ctx.device) / 1e9, 2) if ctx.cuda else None
     mine = busy.overall()
     util_method = "sysfs gpu_busy_percent" if mine is not None else None
-    if not _all_ranks(ctx, mine is not None) and ctx.cuda and args.util_steps > 0:
+    if args.full and not _all_ranks(ctx, mine is not None) and ctx.cuda and args.util_steps > 0:
         # no sysfs counter (on some rank): the kernels' own records, on every rank alike
         kb = kernel_busy(lambda i: tr.step(nxt + 100 + i), args.util_steps, util_devs)
         v = [x for x in kb.values() if x is not None]
@@ -648,7 +705,7 @@ def main():
         util_method = f"kernel-interval union over {args.util_steps} untimed steps (torch.profiler)"
     util = _gather_util(ctx, mine)
     extra = {}
-    if not args.dp:
+    if args.full and not args.dp:
         del tr
         if ctx.cuda:
             torch.cuda.empty_cache()
@@ -667,6 +724,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms, 3),
             "higher_is_better": True,
             "scaling": "weak",

@@ -10,7 +10,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--device", "cpu", "--arch", "resnet18", "--batch", "2", "--image-size", "32",
-        "--steps", "2", "--warmup", "1", "--dtype", "fp32", "--fp32-steps", "0", "--dp-steps", "0"]
+        "--steps", "2", "--warmup", "1", "--dtype", "fp32", "--fp32-steps", "0", "--dp-steps", "0",
+        "--full"]
 
 
 def _port():
@@ -49,6 +50,40 @@ def test_bench_cpu_single(tmp_path):
         assert k in rec, k
     assert rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["warmup"] == 1
     assert abs(rec["value"] - 2 * 1000.0 / rec["ms_per_step"]) / rec["value"] < 1e-2
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the run times its steps and nothing else (no checksum, no secondary pass,
+    no busy %), yet keeps the headline keys; ``--dump-outputs`` writes float32 arrays of the last
+    timed step's loss and state, below 64 MB in all, and a second run with the same arguments
+    reproduces them (same seeded weights and batches; on the CPU engine up to summation order)."""
+    import numpy as np
+    plain = [a for a in ARGS if a != "--full"]
+    recs, dumps = [], []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        r = _run_bare(1, ("--dump-outputs", str(out)), tmp=tmp_path, device_args=plain)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs.append(_record(r))
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    rec = recs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["full"] is False and rec["steps"] == 2 and rec["unit"] == "images/sec"
+    assert abs(rec["value"] - 2 * 1000.0 / rec["ms_per_step"]) / rec["value"] < 1e-2
+    for k in ("checksum", "weights_consistent", "amp_fp16_images_per_sec", "fp32_images_per_sec",
+              "dp_images_per_sec"):
+        assert k not in rec, k
+    assert rec["gpu_util_pct"] is None
+    a, b = dumps
+    assert sorted(a) == ["buffers", "loss", "momentum", "params"] and sorted(b) == sorted(a)
+    assert all(v.dtype == np.float32 and v.ndim == 1 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["params"].size == a["momentum"].size == 4 << 20    # ResNet-18: 11.7 M, sampled
+    assert abs(float(a["loss"][0]) - rec["loss"]) <= 1e-6 * abs(rec["loss"])
+    assert np.isfinite(a["params"]).all() and np.abs(a["momentum"]).max() > 0
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-4, atol=1e-5, err_msg=k)
 
 
 def test_bench_cpu_two_ranks_self_validation(tmp_path):

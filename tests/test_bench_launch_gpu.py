@@ -29,7 +29,7 @@ def test_bench_torchrun_two_ranks(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-fold", "--steps", "2", "--warmup", "1",
-           "--batch", "16", "--image-size", "64"]
+           "--batch", "16", "--image-size", "64", "--full"]
     r = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -70,7 +70,7 @@ def test_bench_torchrun_perturbed_rank_fails(tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-fold", "--steps", "1", "--warmup", "1",
            "--batch", "8", "--image-size", "64", "--fp32-steps", "0", "--amp-steps", "0",
-           "--dp-steps", "0"]
+           "--dp-steps", "0", "--full"]
     r = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "parameters differ across ranks" in r.stderr
 
@@ -93,3 +93,33 @@ def test_bench_bare_gpus2_refused_on_one_gpu_box(tmp_path):
     assert r.returncode == 2, (r.returncode, r.stderr[-2000:])
     assert "needs 2 visible GPUs" in r.stderr and time.time() - t0 < 60
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_plain_run_dumps_native_outputs(tmp_path):
+    """A plain 1-GPU run (no ``--full``) of the native engine: the headline keys and none of the
+    secondary passes, and ``--dump-outputs`` writes the last timed step's loss, f32 master weights,
+    flat momentum and BatchNorm running statistics as float32 arrays (ResNet-50's 25.6 M weights
+    as the fixed 4 Mi-element sample), 64 MB at the most."""
+    import numpy as np
+    env = dict(os.environ, PDA_NO_BUILD="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1", "--batch", "16", "--image-size", "64", "--dump-outputs",
+                        str(out)], cwd=tmp_path, env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert rec["full"] is False and rec["steps"] == 2 and rec["config"]["engine"] == "native"
+    assert rec["unit"] == "images/sec" and rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+    assert abs(rec["value"] - 16 * 1000.0 / rec["ms_per_step"]) / rec["value"] < 1e-2
+    for k in ("checksum", "fp32_images_per_sec", "amp_fp16_images_per_sec", "dp_images_per_sec"):
+        assert k not in rec, k
+    arrs = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(arrs) == ["buffers", "loss", "momentum", "params"]
+    assert all(v.dtype == np.float32 and v.ndim == 1 and np.isfinite(v).all() for v in arrs.values())
+    assert sum(v.nbytes for v in arrs.values()) <= 64 << 20
+    assert arrs["params"].size == arrs["momentum"].size == 4 << 20
+    assert arrs["buffers"].size == 2 * 26560          # running mean + variance of the 53 BN layers
+    assert abs(float(arrs["loss"][0]) - rec["loss"]) <= 1e-6 * abs(rec["loss"])
+    assert np.abs(arrs["momentum"]).max() > 0 and np.abs(arrs["params"]).max() > 0

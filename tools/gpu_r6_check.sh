@@ -15,7 +15,7 @@ if [ -n "$TESTS" ]; then
   tail -25 $O/pytest.log; [ $rc -ne 0 ] && exit $rc
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 600 python -u bench.py ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
   cat $O/bench.json
 fi
 if [ "${PROF:-1}" = 1 ]; then

@@ -28,7 +28,7 @@ for n in ${WORLDS:-2 4 8}; do
       prarg=(); [ -n "$proto" ] && prarg=(--nccl-proto $proto)
       timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
         --master-addr 127.0.0.1 --master-port $port bench.py --gpus $n --steps 20 --warmup 5 \
-        --fp32-steps 0 --amp-steps 0 --dp-steps 0 "${ncarg[@]}" "${prarg[@]}" \
+        --full --fp32-steps 0 --amp-steps 0 --dp-steps 0 "${ncarg[@]}" "${prarg[@]}" \
         > $O/$tag.bench.json 2> $O/$tag.bench.err || { echo "FAIL bench $tag"; tail -5 $O/$tag.bench.err; exit 1; }
       python - "$tag" "$O" <<'PY'
 import json, sys
