@@ -12,7 +12,6 @@
 //   pack_stem      : f32 master [64][7][7][3] -> 16-bit [64][448] (taps x 8 padded channels)
 //   synth_nhwc8    : on-device synthetic ImageNet batch: NHWC, 3 channels padded to 8, 16-bit,
 //                    bit-compatible with data/synthetic.py (label + uniform u) (K12)
-//   nchw_to_nhwc8  : any f32 NCHW image batch -> NHWC8 16-bit model input
 #include "common.h"
 
 namespace {
@@ -289,22 +288,6 @@ __global__ __launch_bounds__(NT) void synth_nhwc8_kernel(const uint32_t* __restr
   }
 }
 
-__global__ __launch_bounds__(NT) void nchw_to_nhwc8_kernel(const float* __restrict__ x, int B, int C,
-                                                           int H, int W, void* __restrict__ out,
-                                                           int dt) {
-  const long long npix = (long long)B * H * W;
-  const int hw = H * W;
-  for (long long i = blockIdx.x * (long long)NT + threadIdx.x; i < npix; i += (long long)gridDim.x * NT) {
-    const int b = (int)(i / hw);
-    const int pix = (int)(i - (long long)b * hw);
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const float v = c < C ? x[((size_t)b * C + c) * hw + pix] : 0.f;
-      st_any(out, (size_t)i * 8 + c, v, dt);
-    }
-  }
-}
-
 // ------------------------------------------------------------------ stem space-to-depth
 // The 7x7/2 stem on a 3-channel image is re-expressed as a 4x4/1 conv (pad 2, output S/2) on the
 // 2x2 space-to-depth image X'[i][j][(p*2+q)*3+c] = x[2i+p][2j+q][c] (12 channels padded to 16):
@@ -530,12 +513,6 @@ int pda_pack_stem_s2d(const float* src, void* dst, int Cout, int dt, hipStream_t
 int pda_stem_s2d_grad(const float* gp, float* g, int Cout, int accumulate, hipStream_t st) {
   TRACKED_LAUNCH(stem_s2d_grad_kernel, dim3((Cout * 147 + 255) / 256), dim3(256), 0, st, gp, g,
                      Cout, accumulate);
-  return (int)hipGetLastError();
-}
-
-int pda_nchw_to_nhwc8(const float* x, int B, int C, int H, int W, void* out, int dt, hipStream_t st) {
-  TRACKED_LAUNCH(nchw_to_nhwc8_kernel, dim3(grid_for((long long)B * H * W, 8192)), dim3(NT), 0, st,
-                     x, B, C, H, W, out, dt);
   return (int)hipGetLastError();
 }
 

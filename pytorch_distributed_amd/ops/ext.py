@@ -117,7 +117,6 @@ _SIGS = {
     "pda_amp_scan": [_V, _L, _V, _V, _V, _V, _V, _F, _F, _I, _V],
     "pda_pack_stem": [_V, _V, _I, _I, _I, _I, _I, _I, _V],
     "pda_synth": [_V, _I, _U, _I, _V, _V, _I, _V, _I, _V],
-    "pda_nchw_to_nhwc8": [_V, _I, _I, _I, _I, _V, _I, _V],
     "pda_synth_s2d": [_V, _I, _U, _I, _V, _V, _I, _V, _I, _V],
     "pda_nchw_to_s2d": [_V, _I, _I, _I, _V, _I, _V],
     "pda_pack_stem_s2d": [_V, _V, _I, _I, _V],

@@ -27,7 +27,7 @@ __all__ = [
     "BnStats", "stats_totals", "bn_finalize_tot", "bn_finalize_partials", "bn_eval_coeffs",
     "bn_apply", "stem_pool", "maxpool_bwd", "tail_pool", "bn_epilogue", "bn_bwd_finish",
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
-    "pack_stem", "synth_batch", "nchw_to_nhwc8", "Workspace",
+    "pack_stem", "synth_batch", "Workspace",
 ]
 
 
@@ -1144,8 +1144,10 @@ def _bn_bwd_tail(ws, part, G, nq, mode, a, y, mean, invstd, gamma, dgamma, dbeta
 # ------------------------------------------------------------------ head / loss
 def xent(logits: torch.Tensor, labels: torch.Tensor, loss_rows, loss, dlog=None,
          gscale: float = 1.0, gdev: Optional[torch.Tensor] = None) -> None:
-    """loss_rows/loss (nullable) = CE(logits, labels); dlog (16-bit [B, ld]) = d(mean CE)/dlogits
-    * gscale * gdev[0] (zero in the padding columns)."""
+    """loss_rows (f32 [B], always written) / loss (nullable) = CE(logits, labels); dlog (16-bit
+    [B, ld]) = d(mean CE)/dlogits * gscale * gdev[0] (zero in the padding columns)."""
+    if loss_rows is None:
+        raise ValueError("xent: loss_rows is required (the kernel writes it on every launch)")
     B, K = logits.shape[0], logits.shape[1]
     ld_out = dlog.shape[1] if dlog is not None else 0
     dt = dt_of(dlog) if dlog is not None else 1
@@ -1215,12 +1217,6 @@ def synth_batch(ids: torch.Tensor, seed: int, split: str, num_classes: int, S: i
     B = ids.numel()
     check(ext.lib().pda_synth(ptr(ids), B, synth_salt(seed, split), num_classes, ptr(keys),
                               ptr(labels), S, ptr(out), dt_of(out), stream(out.device)), "synth")
-
-
-def nchw_to_nhwc8(x, out) -> None:
-    B, C_, H, W = x.shape
-    check(ext.lib().pda_nchw_to_nhwc8(ptr(x), B, C_, H, W, ptr(out), dt_of(out), stream(x.device)),
-          "nchw_to_nhwc8")
 
 
 # ------------------------------------------------------------------ stem (space-to-depth form)
