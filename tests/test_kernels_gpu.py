@@ -2,6 +2,7 @@
 
 Inputs are asymmetric random data rounded to the kernel's 16-bit dtype first, so the
 reference sees exactly the kernel's inputs; tolerances are relative to the output scale.
+The convolutions are also pinned bit for bit on exact integer data: tests/test_conv_exact_gpu.py.
 """
 import math
 
