@@ -25,7 +25,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = os.environ.get("PDA_ARCH", "gfx950")
 
-KERNEL_SRCS = ["conv_gemm.hip", "bn.hip", "misc.hip", "stem.hip", "wgrad_tap.hip"]
+KERNEL_SRCS = ["conv_gemm.hip", "bn.hip", "misc.hip", "stem.hip", "wgrad_tap.hip", "augment.hip"]
 COMM_SRCS = ["comm/rccl_comm.cpp", "comm/reducer.cpp"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"]
 
@@ -39,7 +39,9 @@ def _newer(src: Path, obj: Path, deps) -> bool:
 
 # per-source flags: the conv kernels keep their operand-prologue math in scalar f32 FMAs, which
 # beside MFMAs issue far cheaper than the v_pk_fma_f32 the SLP vectorizer would form
-FILE_FLAGS = {"conv_gemm.hip": ["-fno-slp-vectorize"]}
+# augment.hip evaluates PIL's resampling geometry in double; without FMA contraction its integer tap
+# bounds are those of a float64 numpy evaluation of the same expressions (tests/aug_refs.py)
+FILE_FLAGS = {"conv_gemm.hip": ["-fno-slp-vectorize"], "augment.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: Path, obj: Path, extra, verbose: bool) -> None:

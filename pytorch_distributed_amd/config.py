@@ -48,6 +48,7 @@ class RunConfig:
     bucket_mb: float = 0.0           # DDP bucket cap (0 = framework default)
     sync_bn: bool = False            # SyncBatchNorm in DDP (reference: per-GPU statistics)
     graph: bool = False              # single-GPU native engine: replay each step from a HIP graph
+    aug: str = "cpu"                 # folder data: cpu (PIL in the workers) | gpu (csrc/augment.hip)
 
     def replace(self, **kw) -> "RunConfig":
         return dataclasses.replace(self, **kw)
@@ -84,6 +85,7 @@ _ENV = {
     "MX_BUCKET_MB": ("bucket_mb", float),
     "MX_SYNC_BN": ("sync_bn", lambda s: s not in ("", "0", "false", "False")),
     "MX_GRAPH": ("graph", lambda s: s not in ("", "0", "false", "False")),
+    "MX_AUG": ("aug", str),
 }
 
 
@@ -122,4 +124,6 @@ def config_for(script: str, env: Optional[dict] = None,
         raise ValueError(f"MX_DTYPE must be auto|fp32|bf16|fp16, got {cfg.dtype!r}")
     if cfg.empty_cache not in ("off", "step", "epoch"):
         raise ValueError(f"MX_EMPTY_CACHE must be off|step|epoch, got {cfg.empty_cache!r}")
+    if cfg.aug not in ("cpu", "gpu"):
+        raise ValueError(f"MX_AUG must be cpu|gpu, got {cfg.aug!r}")
     return cfg

@@ -27,7 +27,7 @@ __all__ = [
     "BnStats", "stats_totals", "bn_finalize_tot", "bn_finalize_partials", "bn_eval_coeffs",
     "bn_apply", "stem_pool", "maxpool_bwd", "tail_pool", "bn_epilogue", "bn_bwd_finish",
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
-    "pack_stem", "synth_batch", "Workspace",
+    "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
 ]
 
 
@@ -1235,6 +1235,78 @@ def nchw_to_s2d(x, out) -> None:
     B, C_, S, _ = x.shape
     check(ext.lib().pda_nchw_to_s2d(ptr(x), B, C_, S, ptr(out), dt_of(out), stream(x.device)),
           "nchw_to_s2d")
+
+
+# ------------------------------------------------------------------ folder-image augmentation
+AUG_S2D, AUG_NCHW = 0, 1
+AUG_MAX_SIDE = 32768
+
+
+def aug_check(packed, table_i64, table_f64, out, layout: int) -> Tuple[int, int]:
+    """Host-side validation of an :func:`aug_resize` call; returns (B, S). Pure Python on host
+    tensors (the kernel library is not loaded), and run before anything is launched: the kernel
+    (csrc/augment.hip) trusts every offset, size and box it is given."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("aug_resize: packed must be a contiguous 1-D uint8 tensor")
+    for name, t, dt in (("table_i64", table_i64, torch.int64), ("table_f64", table_f64, torch.float64)):
+        if t.device.type != "cpu":
+            raise ValueError(f"aug_resize: {name} is validated on the host and uploaded by the wrapper")
+        if t.dtype != dt or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous():
+            raise ValueError(f"aug_resize: {name} must be a contiguous [B, 4] {dt} tensor")
+    B = table_i64.shape[0]
+    if B < 1 or table_f64.shape[0] != B:
+        raise ValueError("aug_resize: the tables must have the same B >= 1 rows")
+    if layout == AUG_S2D:
+        if out.dim() != 4 or out.shape[0] != B or out.shape[1] != out.shape[2] or out.shape[3] != 16:
+            raise ValueError(f"aug_resize: s2d output must be [{B}, S/2, S/2, 16], got {tuple(out.shape)}")
+        if out.dtype not in ext.DT:
+            raise ValueError(f"aug_resize: unsupported output dtype {out.dtype}")
+        S = 2 * out.shape[1]
+    elif layout == AUG_NCHW:
+        if out.dim() != 4 or out.shape[0] != B or out.shape[1] != 3 or out.shape[2] != out.shape[3]:
+            raise ValueError(f"aug_resize: NCHW output must be [{B}, 3, S, S], got {tuple(out.shape)}")
+        if out.dtype != torch.float32:
+            raise ValueError("aug_resize: the NCHW layout is f32")
+        S = out.shape[2]
+        if S % 2:
+            raise ValueError(f"aug_resize: the output size must be even, got {S}")
+    else:
+        raise ValueError(f"aug_resize: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
+    if S < 2 or not out.is_contiguous():
+        raise ValueError("aug_resize: the output must be contiguous with S >= 2")
+    if out.device != packed.device:
+        raise ValueError(f"aug_resize: output on {out.device}, packed images on {packed.device}")
+    n = packed.numel()
+    for b, ((off, H, W, _), box) in enumerate(zip(table_i64.tolist(), table_f64.tolist())):
+        if not (1 <= H <= AUG_MAX_SIDE and 1 <= W <= AUG_MAX_SIDE):
+            raise ValueError(f"aug_resize: image {b}: size {W}x{H} outside 1..{AUG_MAX_SIDE}")
+        if off < 0 or off + H * W * 3 > n:
+            raise ValueError(f"aug_resize: image {b}: bytes [{off}, {off + H * W * 3}) outside the "
+                             f"packed buffer of {n}")
+        x0, y0, x1, y1 = box
+        if not all(math.isfinite(v) for v in box):
+            raise ValueError(f"aug_resize: image {b}: non-finite box {box}")
+        if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+            raise ValueError(f"aug_resize: image {b}: box {box} outside the {W}x{H} image")
+    return B, S
+
+
+def aug_resize(packed, table_i64, table_f64, out, layout: int = AUG_S2D) -> None:
+    """Resample / flip / normalise a packed batch of raw uint8 HWC images into ``out`` (one launch,
+    csrc/augment.hip). ``packed``: device bytes; ``table_i64`` [B,4] = byte offset, H, W, flip and
+    ``table_f64`` [B,4] = box x0, y0, x1, y1: HOST tensors (pinned ones upload asynchronously),
+    validated by :func:`aug_check` before the launch."""
+    from ..data.synthetic import MEAN, STD
+    B, S = aug_check(packed, table_i64, table_f64, out, layout)
+    if packed.device.type != "cuda":
+        raise ValueError("aug_resize runs on a GPU; the packed images are on " + str(packed.device))
+    if out.data_ptr() % 16:
+        raise ValueError("aug_resize: the output must be 16-byte aligned")
+    ti = table_i64.to(packed.device, non_blocking=True)
+    tf = table_f64.to(packed.device, non_blocking=True)
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    check(ext.lib().pda_aug_resize(ptr(packed), ptr(ti), ptr(tf), B, S, ptr(out), dt_of(out), layout,
+                                   mean, std, stream(out.device)), "aug_resize")
 
 
 def pack_stem_s2d(src_ohwi, dst) -> None:

@@ -233,25 +233,37 @@ def validate(dataloader, model, criterion, epoch: int, ctx: Context) -> float:
     return c1 / total
 
 
-def _make_folder_loaders(cfg: RunConfig, ctx: Context, per_rank_batch: int):
-    from .data.folder import ImageFolder, train_transform, val_transform
+def _make_folder_loaders(cfg: RunConfig, ctx: Context, per_rank_batch: int, model=None):
+    from .data.folder import ImageFolder, train_params, train_transform, val_params, val_transform
     root = cfg.data.split(":", 1)[1]
-    train_ds = ImageFolder(root, "train", train_transform(cfg.image_size))
-    val_ds = ImageFolder(root, "val", val_transform(cfg.image_size, int(round(cfg.image_size * 256 / 224))))
+    val_resize = int(round(cfg.image_size * 256 / 224))
+    extra = {}
+    if cfg.aug == "gpu":
+        # workers decode only; one HIP kernel (csrc/augment.hip) makes the model-ready batch. The
+        # native engine on one device takes its s2d layout in the model dtype, the torch engine and
+        # DataParallel (which scatters NCHW batches) take NCHW f32
+        s2d = ctx.engine == "native" and not hasattr(model, "replicas")
+        extra = dict(device=ctx.device, image_size=cfg.image_size, layout="s2d" if s2d else "nchw",
+                     dtype=ctx.dtype if s2d else torch.float32)
+        train_ds = ImageFolder(root, "train", raw_params=train_params())
+        val_ds = ImageFolder(root, "val", raw_params=val_params(cfg.image_size, val_resize))
+    else:
+        train_ds = ImageFolder(root, "train", train_transform(cfg.image_size))
+        val_ds = ImageFolder(root, "val", val_transform(cfg.image_size, val_resize))
     train_sampler = val_sampler = None
     if ctx.distributed:
         train_sampler = DistributedSampler(train_ds, ctx.world, ctx.rank, shuffle=True, seed=cfg.seed)
         val_sampler = DistributedSampler(val_ds, ctx.world, ctx.rank, shuffle=True, seed=cfg.seed)
     tl = train_ds.loader(per_rank_batch, sampler=train_sampler, num_workers=cfg.num_workers,
-                         max_steps=cfg.steps_per_epoch)
+                         max_steps=cfg.steps_per_epoch, **extra)
     vl = val_ds.loader(per_rank_batch, sampler=val_sampler, num_workers=cfg.num_workers,
-                       max_steps=cfg.val_steps)
+                       max_steps=cfg.val_steps, **extra)
     return tl, vl, train_sampler
 
 
 def _make_loaders(cfg: RunConfig, ctx: Context, model: nn.Module, per_rank_batch: int):
     if cfg.data.startswith("folder:"):
-        return _make_folder_loaders(cfg, ctx, per_rank_batch)
+        return _make_folder_loaders(cfg, ctx, per_rank_batch, model)
     if cfg.data != "synthetic":
         raise ValueError(f"MX_DATA must be 'synthetic' or 'folder:<root>', got {cfg.data!r}")
     train_ds = SyntheticImageNet("train", cfg.train_samples, cfg.seed, cfg.num_classes, cfg.image_size)
