@@ -34,7 +34,7 @@ class RunConfig:
     # --- framework extensions (MX_* env) ---
     dtype: str = "auto"              # auto | fp32 | bf16 | fp16 (auto: fp32 = the reference's precision; ddp_amp: fp16)
     device: str = "auto"             # auto | cuda | cpu
-    data: str = "synthetic"          # synthetic | folder:<path>
+    data: str = "synthetic"          # synthetic | folder:<path> | packed:<dir>
     image_size: int = 224
     train_samples: int = 1_281_167   # ImageNet-1k train size (virtual synthetic samples)
     val_samples: int = 50_000
@@ -49,6 +49,7 @@ class RunConfig:
     sync_bn: bool = False            # SyncBatchNorm in DDP (reference: per-GPU statistics)
     graph: bool = False              # single-GPU native engine: replay each step from a HIP graph
     aug: str = "cpu"                 # folder data: cpu (PIL in the workers) | gpu (csrc/augment.hip)
+    pack_resident: str = "auto"      # packed data: auto | device (pixels in HBM) | host (per-batch upload)
 
     def replace(self, **kw) -> "RunConfig":
         return dataclasses.replace(self, **kw)
@@ -86,6 +87,7 @@ _ENV = {
     "MX_SYNC_BN": ("sync_bn", lambda s: s not in ("", "0", "false", "False")),
     "MX_GRAPH": ("graph", lambda s: s not in ("", "0", "false", "False")),
     "MX_AUG": ("aug", str),
+    "MX_PACK_RESIDENT": ("pack_resident", str),
 }
 
 
@@ -126,4 +128,8 @@ def config_for(script: str, env: Optional[dict] = None,
         raise ValueError(f"MX_EMPTY_CACHE must be off|step|epoch, got {cfg.empty_cache!r}")
     if cfg.aug not in ("cpu", "gpu"):
         raise ValueError(f"MX_AUG must be cpu|gpu, got {cfg.aug!r}")
+    if cfg.pack_resident not in ("auto", "device", "host"):
+        raise ValueError(f"MX_PACK_RESIDENT must be auto|device|host, got {cfg.pack_resident!r}")
+    if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:
+        raise ValueError("MX_DATA=packed:<dir> needs the directory that holds train.pack and val.pack")
     return cfg

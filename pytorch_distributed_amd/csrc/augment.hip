@@ -1,6 +1,8 @@
 // Folder-image augmentation for gfx950: resample (PIL's bilinear / triangle filter on a real-valued
 // box), horizontal flip, normalise and store model-ready, in one launch over a packed batch of raw
-// uint8 HWC images of different sizes (data/folder.py raw mode; K12).
+// uint8 HWC images of different sizes (data/folder.py raw mode; K12). A second, small kernel
+// (aug_draw_kernel, below) draws the crop boxes and flips on the device for the packed data path
+// (data/packed.py), whose decoded images stay resident and need no per-step host pipeline.
 //
 //   R[oy][ox][c] = sum_y kv(oy,y) * sum_x kh(ox,x) * I[y][x][c]          (levels 0..255, no rounding)
 //   out = (R[oy][flip ? S-1-ox : ox][c] / 255 - mean[c]) / std[c]
@@ -219,6 +221,108 @@ __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __res
   }
 }
 
+// ---- crop draw (packed data path, data/packed.py) ---------------------------------------------
+// One thread per sample: looks the sample's record up in the dataset index [N][4] = (byte offset, H,
+// W, label) and writes the rows of the tables aug_resize_kernel reads, plus the label. Train mode is
+// data/folder.py train_crop_params (RandomResizedCrop + flip) in double; val mode is val_crop_params.
+// The uniforms are counter-based: u(k) = hash32(ekey ^ (k+1)*0x27D4EB2F) / 2^32 with
+//   key = hash32(id*2654435761 + salt), salt = (seed*97 + split_id)*0x632BE5AB   (as the synthetic data)
+//   ekey = hash32(key ^ (epoch*0x9E3779B9 + 0x85EBCA6B))
+// and fixed counters: attempt a draws area 4a, ratio 4a+1, row 4a+2, column 4a+3; the flip is 40. A
+// sample's crop therefore depends on (seed, split, epoch, id) alone, not on where in which batch of
+// which rank it is drawn. tests/packed_refs.py evaluates the same expressions in Python float64.
+struct AugDraw {
+  long long N;
+  uint32_t salt, epoch;
+  int mode, S, resize;
+  double s0, s1, l0, l1, r0, r1;   // scale bounds, log ratio bounds, ratio bounds
+};
+
+__device__ __forceinline__ double aug_u(uint32_t ekey, uint32_t k) {
+  return (double)hash32(ekey ^ ((k + 1u) * 0x27D4EB2Fu)) * (1.0 / 4294967296.0);   // exact in double
+}
+
+__global__ __launch_bounds__(AUG_NT) void aug_draw_kernel(const long long* __restrict__ ids,
+                                                          const long long* __restrict__ index,
+                                                          const long long* __restrict__ batch_off,
+                                                          int B, AugDraw d, long long* __restrict__ ti,
+                                                          double* __restrict__ tf,
+                                                          long long* __restrict__ labels) {
+  const int b = blockIdx.x * AUG_NT + threadIdx.x;
+  if (b >= B) return;
+  long long id = ids[b];
+  // the wrapper checked the ids on the host; a stray one must still not read outside the index
+  if ((unsigned long long)id >= (unsigned long long)d.N) id = 0;
+  const long long* rec = index + id * 4;
+  const long long off = batch_off != nullptr ? batch_off[b] : rec[0];
+  const int H = (int)rec[1], W = (int)rec[2];
+  double x0, y0, x1, y1;
+  int flip = 0;
+  if (d.mode == 0) {
+    const uint32_t key = hash32((uint32_t)id * 2654435761u + d.salt);
+    const uint32_t ekey = hash32(key ^ (d.epoch * 0x9E3779B9u + 0x85EBCA6Bu));
+    const double area = (double)(W * H);
+    int w = 0, h = 0, i = 0, j = 0;
+    bool ok = false;
+    for (uint32_t a = 0; a < 10 && !ok; ++a) {
+      const double target = area * (d.s0 + (d.s1 - d.s0) * aug_u(ekey, 4 * a));
+      const double ar = exp(d.l0 + (d.l1 - d.l0) * aug_u(ekey, 4 * a + 1));
+      w = (int)rint(sqrt(target * ar));
+      h = (int)rint(sqrt(target / ar));
+      if (0 < w && w <= W && 0 < h && h <= H) {
+        i = (int)(aug_u(ekey, 4 * a + 2) * (double)(H - h + 1));
+        j = (int)(aug_u(ekey, 4 * a + 3) * (double)(W - w + 1));
+        ok = true;
+      }
+    }
+    if (!ok) {   // centre crop at the clamped ratio
+      const double in_ratio = (double)W / (double)H;
+      if (in_ratio < d.r0) {
+        w = W;
+        h = (int)rint((double)W / d.r0);
+      } else if (in_ratio > d.r1) {
+        h = H;
+        w = (int)rint((double)H * d.r1);
+      } else {
+        w = W;
+        h = H;
+      }
+      w = w < 1 ? 1 : (w > W ? W : w);   // no-ops for r0 <= r1; the box must stay inside the image
+      h = h < 1 ? 1 : (h > H ? H : h);
+      i = (H - h) / 2;
+      j = (W - w) / 2;
+    }
+    x0 = (double)j;
+    y0 = (double)i;
+    x1 = (double)(j + w);
+    y1 = (double)(i + h);
+    flip = aug_u(ekey, 40) < 0.5 ? 1 : 0;
+  } else {
+    int nw, nh;
+    if (W <= H) {
+      nw = d.resize;
+      nh = (int)((double)((long long)d.resize * H) / (double)W);
+    } else {
+      nh = d.resize;
+      nw = (int)((double)((long long)d.resize * W) / (double)H);
+    }
+    const int top = (int)rint((double)(nh - d.S) / 2.0), left = (int)rint((double)(nw - d.S) / 2.0);
+    x0 = (double)((long long)left * W) / (double)nw;
+    y0 = (double)((long long)top * H) / (double)nh;
+    x1 = (double)((long long)(left + d.S) * W) / (double)nw;
+    y1 = (double)((long long)(top + d.S) * H) / (double)nh;
+  }
+  ti[b * 4 + 0] = off;
+  ti[b * 4 + 1] = H;
+  ti[b * 4 + 2] = W;
+  ti[b * 4 + 3] = flip;
+  tf[b * 4 + 0] = x0;
+  tf[b * 4 + 1] = y0;
+  tf[b * 4 + 2] = x1;
+  tf[b * 4 + 3] = y1;
+  labels[b] = rec[3];
+}
+
 }  // namespace
 
 extern "C" {
@@ -250,6 +354,36 @@ int pda_aug_resize(const void* packed, const long long* ti, const double* tf, in
   else if (dt == DT_F32) AUG_K(DT_F32, 0);
   else return -2;
 #undef AUG_K
+  return (int)hipGetLastError();
+}
+
+// ids: device int64 [B], every one in [0, N); index: device int64 [N][4] = byte offset, H, W, label,
+// validated on the host when the file was opened (data/packed.py); batch_off: device int64 [B] byte
+// offsets that replace the index's (host residency), or null. mode 0: train draw with scale bounds
+// s0 <= s1 and ratio bounds r0 <= r1; 1: val box of Resize(resize) -> CenterCrop(S), resize >= S.
+// Writes ti [B][4], tf [B][4] (pda_aug_resize's tables) and labels [B].
+int pda_aug_draw(const long long* ids, const long long* index, const long long* batch_off, int B,
+                 long long N, unsigned seed, int split_id, unsigned epoch, int mode, int S, int resize,
+                 double s0, double s1, double r0, double r1, long long* ti, double* tf,
+                 long long* labels, hipStream_t st) {
+  if (B < 1 || N < 1 || S < 2 || (mode != 0 && mode != 1)) return -2;
+  if (mode == 0 && !(0.0 < s0 && s0 <= s1 && s1 <= 1.0 && 1e-3 <= r0 && r0 <= r1 && r1 <= 1e3)) return -2;
+  if (mode == 1 && (resize < S || resize > 65536)) return -2;
+  AugDraw d;
+  d.N = N;
+  d.salt = (seed * 97u + (unsigned)split_id) * 0x632BE5ABu;
+  d.epoch = epoch;
+  d.mode = mode;
+  d.S = S;
+  d.resize = resize;
+  d.s0 = s0;
+  d.s1 = s1;
+  d.l0 = log(r0);
+  d.l1 = log(r1);
+  d.r0 = r0;
+  d.r1 = r1;
+  const dim3 grid((unsigned)((B + AUG_NT - 1) / AUG_NT)), block(AUG_NT);
+  TRACKED_LAUNCH(aug_draw_kernel, grid, block, 0, st, ids, index, batch_off, B, d, ti, tf, labels);
   return (int)hipGetLastError();
 }
 

@@ -236,15 +236,6 @@ __global__ void pack_stem_kernel(const float* __restrict__ src, void* __restrict
 }
 
 // ------------------------------------------------------------------ data
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
 __constant__ float c_mean[3] = {0.485f, 0.456f, 0.406f};
 __constant__ float c_istd[3] = {1.f / 0.229f, 1.f / 0.224f, 1.f / 0.225f};
 

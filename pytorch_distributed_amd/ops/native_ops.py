@@ -28,6 +28,7 @@ __all__ = [
     "bn_apply", "stem_pool", "maxpool_bwd", "tail_pool", "bn_epilogue", "bn_bwd_finish",
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
+    "aug_draw", "aug_resize_dev",
 ]
 
 
@@ -1307,6 +1308,93 @@ def aug_resize(packed, table_i64, table_f64, out, layout: int = AUG_S2D) -> None
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
     check(ext.lib().pda_aug_resize(ptr(packed), ptr(ti), ptr(tf), B, S, ptr(out), dt_of(out), layout,
                                    mean, std, stream(out.device)), "aug_resize")
+
+
+AUG_TRAIN, AUG_VAL = 0, 1
+
+
+def aug_draw(ids, index_dev, N: int, seed: int, split: str, epoch: int, mode: int, S: int,
+             resize: int = 0, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), batch_off=None):
+    """Crop boxes, flips and labels of the samples ``ids`` of a packed dataset, drawn on the device
+    (one launch, csrc/augment.hip ``aug_draw_kernel``): returns device ``(ti [B,4] int64 = byte
+    offset, H, W, flip; tf [B,4] float64 = x0, y0, x1, y1; labels [B] int64)``, the tables of
+    :func:`aug_resize_dev`.
+
+    ``ids``: HOST int64 [B], checked here against ``N`` and uploaded (pinned ones asynchronously);
+    ``index_dev``: device int64 [N,4] = byte offset, H, W, label, validated when the file was opened
+    (``data.packed.PackedImages``); ``batch_off``: device int64 [B] byte offsets that replace the
+    index's (host residency). ``mode`` ``AUG_TRAIN``: ``data.folder.train_crop_params`` with
+    uniforms that are a pure function of (seed, split, epoch, id); ``AUG_VAL``:
+    ``val_crop_params(W, H, S, resize)``."""
+    from ..data.synthetic import SPLIT_ID
+    if ids.device.type != "cpu" or ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("aug_draw: ids must be a contiguous host int64 [B] tensor (checked on the host)")
+    B = ids.numel()
+    if B < 1:
+        raise ValueError("aug_draw: empty batch")
+    if index_dev.device.type != "cuda":
+        raise ValueError(f"aug_draw runs on a GPU; the index is on {index_dev.device}")
+    if (index_dev.dtype != torch.int64 or index_dev.dim() != 2 or index_dev.shape[1] != 4
+            or not index_dev.is_contiguous() or index_dev.shape[0] != N or N < 1):
+        raise ValueError(f"aug_draw: the index must be a contiguous device int64 [{N}, 4] tensor")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < 0 or hi >= N:
+        raise ValueError(f"aug_draw: sample ids span [{lo}, {hi}], outside the {N} records")
+    if batch_off is not None and (batch_off.device != index_dev.device or batch_off.dtype != torch.int64
+                                  or batch_off.shape != (B,) or not batch_off.is_contiguous()):
+        raise ValueError(f"aug_draw: batch_off must be a contiguous int64 [{B}] tensor on {index_dev.device}")
+    if split not in SPLIT_ID:
+        raise ValueError(f"aug_draw: split must be one of {sorted(SPLIT_ID)}, got {split!r}")
+    if mode not in (AUG_TRAIN, AUG_VAL) or S < 2 or epoch < 0:
+        raise ValueError(f"aug_draw: mode {mode}, S {S}, epoch {epoch}")
+    s0, s1, r0, r1 = float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1])
+    if mode == AUG_TRAIN and not (0.0 < s0 <= s1 <= 1.0 and 1e-3 <= r0 <= r1 <= 1e3):
+        raise ValueError(f"aug_draw: scale {scale} must lie in (0, 1] and ratio {ratio} in [1e-3, 1e3], "
+                         "both ascending")
+    if mode == AUG_VAL and not S <= resize <= 65536:
+        raise ValueError(f"aug_draw: val mode resizes to {resize}, below the crop size {S} (or above 65536)")
+    dev = index_dev.device
+    ti = torch.empty(B, 4, dtype=torch.int64, device=dev)
+    tf = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    labels = torch.empty(B, dtype=torch.int64, device=dev)
+    ids_dev = ids.to(dev, non_blocking=True)
+    check(ext.lib().pda_aug_draw(ptr(ids_dev), ptr(index_dev), ptr(batch_off), B, N,
+                                 seed & 0xFFFFFFFF, SPLIT_ID[split], epoch & 0xFFFFFFFF, mode, S,
+                                 int(resize), s0, s1, r0, r1, ptr(ti), ptr(tf), ptr(labels),
+                                 stream(dev)), "aug_draw")
+    return ti, tf, labels
+
+
+def aug_resize_dev(packed, ti_dev, tf_dev, out, layout: int = AUG_S2D) -> None:
+    """:func:`aug_resize` on DEVICE tables that :func:`aug_draw` wrote from a validated index (the
+    kernel trusts them; nothing is read back): resample / flip / normalise into ``out``."""
+    from ..data.synthetic import MEAN, STD
+    if packed.device.type != "cuda":
+        raise ValueError("aug_resize_dev runs on a GPU; the packed images are on " + str(packed.device))
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("aug_resize_dev: packed must be a contiguous 1-D uint8 tensor")
+    for name, t, dt in (("ti_dev", ti_dev, torch.int64), ("tf_dev", tf_dev, torch.float64)):
+        if t.device != packed.device or out.device != packed.device:
+            raise ValueError(f"aug_resize_dev: {name} and the output must be on {packed.device}")
+        if t.dtype != dt or t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous():
+            raise ValueError(f"aug_resize_dev: {name} must be a contiguous [B, 4] {dt} tensor")
+    B = ti_dev.shape[0]
+    if B < 1 or tf_dev.shape[0] != B:
+        raise ValueError("aug_resize_dev: the tables must have the same B >= 1 rows")
+    if layout == AUG_S2D:
+        S = 2 * out.shape[1] if out.dim() == 4 else 0
+        ok = out.dim() == 4 and tuple(out.shape) == (B, S // 2, S // 2, 16) and out.dtype in ext.DT
+    elif layout == AUG_NCHW:
+        S = out.shape[2] if out.dim() == 4 else 0
+        ok = out.dim() == 4 and tuple(out.shape) == (B, 3, S, S) and out.dtype == torch.float32
+    else:
+        raise ValueError(f"aug_resize_dev: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
+    if not ok or S < 2 or S % 2 or not out.is_contiguous() or out.data_ptr() % 16:
+        raise ValueError(f"aug_resize_dev: output {tuple(out.shape)} {out.dtype} does not fit layout "
+                         f"{layout} for {B} images (even S >= 2, contiguous, 16-byte aligned)")
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    check(ext.lib().pda_aug_resize(ptr(packed), ptr(ti_dev), ptr(tf_dev), B, S, ptr(out), dt_of(out),
+                                   layout, mean, std, stream(out.device)), "aug_resize_dev")
 
 
 def pack_stem_s2d(src_ohwi, dst) -> None:

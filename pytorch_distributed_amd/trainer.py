@@ -261,11 +261,38 @@ def _make_folder_loaders(cfg: RunConfig, ctx: Context, per_rank_batch: int, mode
     return tl, vl, train_sampler
 
 
+def _make_packed_loaders(cfg: RunConfig, ctx: Context, per_rank_batch: int, model=None):
+    """``MX_DATA=packed:<dir>``: ``<dir>/train.pack`` and ``<dir>/val.pack`` (data/packed.py), made
+    resident per ``MX_PACK_RESIDENT``; crops are drawn and resampled on the GPU, no worker
+    processes. Layout and dtype as for ``MX_AUG=gpu``. Under DDP every rank holds its own copy."""
+    from .data.packed import PackedImages, PackedLoader
+    root = cfg.data.split(":", 1)[1]
+    if ctx.device.type != "cuda":
+        raise ValueError(f"MX_DATA=packed: resamples on the GPU (csrc/augment.hip); the device is "
+                         f"{ctx.device}. Use MX_DATA=folder:<root> on a CPU device.")
+    s2d = ctx.engine == "native" and not hasattr(model, "replicas")
+    kw = dict(dtype=ctx.dtype if s2d else torch.float32, layout="s2d" if s2d else "nchw",
+              image_size=cfg.image_size, resize=int(round(cfg.image_size * 256 / 224)), seed=cfg.seed)
+    loaders, train_sampler = [], None
+    for split, max_steps in (("train", cfg.steps_per_epoch), ("val", cfg.val_steps)):
+        images = PackedImages(os.path.join(root, split + ".pack"))
+        sampler = None
+        if ctx.distributed:
+            sampler = DistributedSampler(images, ctx.world, ctx.rank, shuffle=True, seed=cfg.seed)
+            train_sampler = train_sampler or sampler
+        loaders.append(PackedLoader(images.to_device(ctx.device, cfg.pack_resident), split,
+                                    per_rank_batch, sampler=sampler, max_steps=max_steps, **kw))
+    return loaders[0], loaders[1], train_sampler
+
+
 def _make_loaders(cfg: RunConfig, ctx: Context, model: nn.Module, per_rank_batch: int):
     if cfg.data.startswith("folder:"):
         return _make_folder_loaders(cfg, ctx, per_rank_batch, model)
+    if cfg.data.startswith("packed:"):
+        return _make_packed_loaders(cfg, ctx, per_rank_batch, model)
     if cfg.data != "synthetic":
-        raise ValueError(f"MX_DATA must be 'synthetic' or 'folder:<root>', got {cfg.data!r}")
+        raise ValueError(f"MX_DATA must be 'synthetic', 'folder:<root>' or 'packed:<dir>', got "
+                         f"{cfg.data!r}")
     train_ds = SyntheticImageNet("train", cfg.train_samples, cfg.seed, cfg.num_classes, cfg.image_size)
     val_ds = SyntheticImageNet("val", cfg.val_samples, cfg.seed, cfg.num_classes, cfg.image_size)
     if ctx.distributed:
@@ -373,6 +400,8 @@ def run(cfg: RunConfig, mode: str, local_rank: int = 0, nprocs: Optional[int] = 
         t1 = time.time()
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
+        if hasattr(train_loader, "set_epoch"):      # packed data: the epoch of the crop draws
+            train_loader.set_epoch(epoch)
         from .utils.gpu_util import BusySampler, StepBusy, busy_path
         devs = ([ctx.device.index if ctx.device.index is not None else torch.cuda.current_device()]
                 if ctx.device.type == "cuda" else [])
