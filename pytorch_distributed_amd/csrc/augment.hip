@@ -22,6 +22,14 @@
 // all rows of the strip. Tap weights are evaluated where they are used (no per-tap table, so no
 // limit on the tap count); sums are sequential f32 fmas in a fixed order: deterministic, no atomics.
 // Source bytes are read one at a time, so image offsets and row pitches (3*W) need no alignment.
+//
+// Source format 1 (FMT, version-2 packed files of data/packed.py) is YCbCr 4:2:0: a record is the Y
+// plane [H][W], then the interleaved CbCr plane [Hc][Wc][2] at half resolution (Hc = (H+1)/2,
+// Wc = (W+1)/2). The stored image is I = (Y[y][x], Cb[y>>1][x>>1] - 128, Cr[y>>1][x>>1] - 128)
+// (nearest chroma; the subtraction is exact in f32). The colour transform is linear, so the same
+// tap loops filter these three planes and the store stage converts once per output pixel:
+//   R = Y + 1.402 cr, G = Y - 0.344136 cb - 0.714136 cr, B = Y + 1.772 cb, clamped to [0, 255],
+// then normalised as above. A grey image has filtered chroma of exactly 0 and R = G = B = Y.
 #include "common.h"
 
 namespace {
@@ -63,8 +71,16 @@ __device__ __forceinline__ double aug_inv_sum(const AugAxis& ax, double center, 
   return 1.0 / s;
 }
 
-// LAYOUT 0: s2d [B][S/2][S/2][16] of DT; 1: NCHW f32 [B][3][S][S]
-template <int DT, int LAYOUT>
+// filtered (Y, Cb-128, Cr-128) levels -> channel c of the clamped RGB levels (format 1)
+__device__ __forceinline__ float aug_rgb(float y, float cb, float cr, int c) {
+  const float v = c == 0   ? __builtin_fmaf(1.402f, cr, y)
+                  : c == 1 ? __builtin_fmaf(-0.714136f, cr, __builtin_fmaf(-0.344136f, cb, y))
+                           : __builtin_fmaf(1.772f, cb, y);
+  return fminf(fmaxf(v, 0.f), 255.f);
+}
+
+// LAYOUT 0: s2d [B][S/2][S/2][16] of DT; 1: NCHW f32 [B][3][S][S]. FMT 0: HWC RGB; 1: YCbCr 4:2:0
+template <int DT, int LAYOUT, int FMT>
 __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __restrict__ packed,
                                                             const long long* __restrict__ ti,
                                                             const double* __restrict__ tf, int S,
@@ -146,13 +162,27 @@ __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __res
       const int yy = i / tw, ox = i - yy * tw;
       const int xa = s_xmin[ox], xb = s_xmax[ox];
       const double c = s_xc[ox], inv = s_xinv[ox];
-      const uint8_t* p = img + ((size_t)(yc + yy) * W + xa) * 3;
       float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-      for (int x = xa; x < xb; ++x, p += 3) {
-        const float k = (float)(aug_w(ax, c, x) * inv);
-        a0 = __builtin_fmaf(k, (float)p[0], a0);
-        a1 = __builtin_fmaf(k, (float)p[1], a1);
-        a2 = __builtin_fmaf(k, (float)p[2], a2);
+      if constexpr (FMT == 0) {
+        const uint8_t* p = img + ((size_t)(yc + yy) * W + xa) * 3;
+        for (int x = xa; x < xb; ++x, p += 3) {
+          const float k = (float)(aug_w(ax, c, x) * inv);
+          a0 = __builtin_fmaf(k, (float)p[0], a0);
+          a1 = __builtin_fmaf(k, (float)p[1], a1);
+          a2 = __builtin_fmaf(k, (float)p[2], a2);
+        }
+      } else {
+        // y < H and x < W, so (y>>1, x>>1) lies inside the [Hc][Wc] chroma plane
+        const int y = yc + yy, Wc = (W + 1) >> 1;
+        const uint8_t* py = img + (size_t)y * W;
+        const uint8_t* pc = img + (size_t)H * W + (size_t)(y >> 1) * Wc * 2;
+        for (int x = xa; x < xb; ++x) {
+          const float k = (float)(aug_w(ax, c, x) * inv);
+          const uint8_t* q = pc + (x >> 1) * 2;
+          a0 = __builtin_fmaf(k, (float)py[x], a0);
+          a1 = __builtin_fmaf(k, (float)q[0] - 128.f, a1);
+          a2 = __builtin_fmaf(k, (float)q[1] - 128.f, a2);
+        }
       }
       float* d = s_row + yy * tw3 + ox * 3;
       d[0] = a0;
@@ -177,15 +207,21 @@ __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __res
     __syncthreads();
   }
 
-  // normalise into the tile image [row][column][3] (unflipped)
+  // normalise into the tile image [row][column][3] (unflipped); format 1 leaves the filtered
+  // YCbCr levels there: a thread holds no whole pixel, the store stage converts and normalises
 #pragma unroll
   for (int m = 0; m < AUG_CPT; ++m) {
     const int q = tid + m * AUG_NT;
     if (q < tw3) {
       const int c = q % 3;
 #pragma unroll
-      for (int r = 0; r < AUG_TR; ++r)
-        if (r < tr) s_row[r * tw3 + q] = __builtin_fmaf(acc[m][r], nm.a[c], nm.b[c]);
+      for (int r = 0; r < AUG_TR; ++r) {
+        if constexpr (FMT == 0) {
+          if (r < tr) s_row[r * tw3 + q] = __builtin_fmaf(acc[m][r], nm.a[c], nm.b[c]);
+        } else {
+          if (r < tr) s_row[r * tw3 + q] = acc[m][r];
+        }
+      }
     }
   }
   __syncthreads();
@@ -202,7 +238,10 @@ __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __res
         const int col = 2 * j + (pq & 1);
         const float* s = s_row + (2 * ri + (pq >> 1)) * tw3 + (flip ? tw - 1 - col : col) * 3;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) h[pq * 3 + c] = s[c];
+        for (int c = 0; c < 3; ++c) {
+          if constexpr (FMT == 0) h[pq * 3 + c] = s[c];
+          else h[pq * 3 + c] = __builtin_fmaf(aug_rgb(s[0], s[1], s[2], c), nm.a[c], nm.b[c]);
+        }
       }
 #pragma unroll
       for (int c = 12; c < 16; ++c) h[c] = 0.f;
@@ -215,8 +254,14 @@ __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __res
     for (int i = tid; i < 3 * tr * tw; i += AUG_NT) {
       const int c = i / (tr * tw), rem = i - c * (tr * tw);
       const int r = rem / tw, j = rem - r * tw;
-      o[(((size_t)b * 3 + c) * S + (oy0 + r)) * S + oxs + j] =
-          s_row[r * tw3 + (flip ? tw - 1 - j : j) * 3 + c];
+      if constexpr (FMT == 0) {
+        o[(((size_t)b * 3 + c) * S + (oy0 + r)) * S + oxs + j] =
+            s_row[r * tw3 + (flip ? tw - 1 - j : j) * 3 + c];
+      } else {
+        const float* s = s_row + r * tw3 + (flip ? tw - 1 - j : j) * 3;
+        o[(((size_t)b * 3 + c) * S + (oy0 + r)) * S + oxs + j] =
+            __builtin_fmaf(aug_rgb(s[0], s[1], s[2], c), nm.a[c], nm.b[c]);
+      }
     }
   }
 }
@@ -329,11 +374,14 @@ extern "C" {
 
 // packed: device bytes; ti: device int64 [B][4] = byte offset, H, W, flip; tf: device f64 [B][4] =
 // x0, y0, x1, y1; mean / std: HOST float[3]. layout 0: s2d [B][S/2][S/2][16] of dtype dt (16-B
-// aligned), 1: NCHW f32. The tables must have been validated by the caller (ops/native_ops.py
-// aug_check): the kernel trusts offsets, sizes and boxes.
-int pda_aug_resize(const void* packed, const long long* ti, const double* tf, int B, int S, void* out,
-                   int dt, int layout, const float* mean, const float* std, hipStream_t st) {
-  if (B < 1 || S < 2 || (S & 1) || (layout != 0 && layout != 1)) return -2;
+// aligned), 1: NCHW f32. fmt 0: records are HWC RGB (3*H*W bytes); 1: YCbCr 4:2:0 (Y plane, then
+// the interleaved half-resolution CbCr plane: H*W + 2*((H+1)/2)*((W+1)/2) bytes). The tables must
+// have been validated by the caller (ops/native_ops.py aug_check): the kernel trusts offsets, sizes
+// and boxes.
+int pda_aug_resize_fmt(const void* packed, const long long* ti, const double* tf, int B, int S,
+                       void* out, int dt, int layout, int fmt, const float* mean, const float* std,
+                       hipStream_t st) {
+  if (B < 1 || S < 2 || (S & 1) || (layout != 0 && layout != 1) || (fmt != 0 && fmt != 1)) return -2;
   if (layout == 1 && dt != DT_F32) return -2;
   if (layout == 0 && ((uintptr_t)out & 15)) return -2;
   AugNorm nm;
@@ -346,15 +394,27 @@ int pda_aug_resize(const void* packed, const long long* ti, const double* tf, in
   if (nblk > 0x7fffffffLL) return -2;
   const dim3 grid((unsigned)nblk), block(AUG_NT);
   const uint8_t* src = reinterpret_cast<const uint8_t*>(packed);
-#define AUG_K(D, L) \
-  TRACKED_LAUNCH((aug_resize_kernel<D, L>), grid, block, 0, st, src, ti, tf, S, nstrips, ntx, out, nm)
+#define AUG_K1(D, L, F) \
+  TRACKED_LAUNCH((aug_resize_kernel<D, L, F>), grid, block, 0, st, src, ti, tf, S, nstrips, ntx, out, nm)
+#define AUG_K(D, L)                \
+  do {                             \
+    if (fmt == 0) AUG_K1(D, L, 0); \
+    else AUG_K1(D, L, 1);          \
+  } while (0)
   if (layout == 1) AUG_K(DT_F32, 1);
   else if (dt == DT_BF16) AUG_K(DT_BF16, 0);
   else if (dt == DT_F16) AUG_K(DT_F16, 0);
   else if (dt == DT_F32) AUG_K(DT_F32, 0);
   else return -2;
 #undef AUG_K
+#undef AUG_K1
   return (int)hipGetLastError();
+}
+
+// RGB records: the folder path and version-1 packed files
+int pda_aug_resize(const void* packed, const long long* ti, const double* tf, int B, int S, void* out,
+                   int dt, int layout, const float* mean, const float* std, hipStream_t st) {
+  return pda_aug_resize_fmt(packed, ti, tf, B, S, out, dt, layout, 0, mean, std, st);
 }
 
 // ids: device int64 [B], every one in [0, N); index: device int64 [N][4] = byte offset, H, W, label,

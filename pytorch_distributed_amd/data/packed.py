@@ -17,7 +17,24 @@ File layout, little-endian::
                     index offset, pixels offset, pixels bytes
     names           JSON list of class names in ImageFolder's sorted-directory order
     index           int64 [N, 4]: byte offset into the pixel section, H, W, label
-    pixels          every image's HWC uint8 RGB bytes back to back
+    pixels          every image's record back to back
+
+The version is the record format. Version 1 (``fmt="rgb"``): a record is the image's HWC uint8 RGB
+bytes, ``3*H*W``. Version 2 (``fmt="yuv420"``): YCbCr 4:2:0, the layout almost every source JPEG
+already has: the Y plane ``[H, W]``, then the CbCr plane ``[Hc, Wc, 2]`` (Cb and Cr interleaved) with
+``Hc = (H+1)//2``, ``Wc = (W+1)//2``; ``H*W + 2*Hc*Wc`` bytes, half of the RGB record. H and W in the
+index are the luma size in both. The encoding is exact integer arithmetic on the shrunk RGB image
+(16-bit JFIF weights, :func:`encode_yuv420`): a 2x2 block of luma rows ``2j, 2j+1`` and columns
+``2i, 2i+1`` shares one chroma sample, an odd last row or column is repeated. What a version-2 file
+STORES is the real-valued image, never rounded,
+
+    cb = Cb[y>>1][x>>1] - 128,  cr = Cr[y>>1][x>>1] - 128                   (nearest chroma)
+    R = Y + 1.402 cr,   G = Y - 0.344136 cb - 0.714136 cr,   B = Y + 1.772 cb
+
+which ``aug_resize_kernel`` resamples by filtering the three stored planes and converting (and
+clamping to 0..255) once per output pixel. A grey pixel stores ``Y = v, Cb = Cr = 128`` and decodes
+exactly; a constant colour comes back, after the clamp, within 1.384 levels (all 2^24 checked). The
+cost is chroma at half resolution.
 
 Shrinking the training images once changes what ``RandomResizedCrop`` samples from: the crop is
 drawn on the stored image, so a crop that covers less than ``short_side``-scale detail is enlarged
@@ -39,11 +56,12 @@ import torch
 
 from .sampler import SequentialIndices
 
-__all__ = ["MAGIC", "VERSION", "shrunk_size", "write_packed", "PackedImages", "PackedStore",
-           "PackedLoader"]
+__all__ = ["MAGIC", "VERSION", "FORMATS", "shrunk_size", "encode_yuv420", "write_packed",
+           "PackedImages", "PackedStore", "PackedLoader"]
 
 MAGIC = b"PDAPACK\0"
-VERSION = 1
+VERSION = 1                                  # the version of an RGB file
+FORMATS = {"rgb": 1, "yuv420": 2}            # record format -> file version
 _HEADER = struct.Struct("<8s8Q")
 STAGE_BYTES = 256 << 20       # bound on the pinned staging memory of the device-residency upload
 
@@ -58,9 +76,31 @@ def shrunk_size(W: int, H: int, short_side: int) -> Tuple[int, int]:
     return int(short_side * W / H), short_side
 
 
-def _decode(job) -> np.ndarray:
+def encode_yuv420(a: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """``(Y [H, W], CbCr [Hc, Wc, 2])`` uint8 of a uint8 HxWx3 RGB image, in exact integers::
+
+        Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+        cb = -11059 R - 21709 G + 32768 B ;  cr = 32768 R - 27439 G - 5329 B     (per pixel)
+        Cb[j][i] = clip((sum of cb over the 2x2 block + (128 << 18) + (1 << 17)) >> 18, 0, 255)
+
+    and Cr likewise; an odd last row or column is repeated into the block. The shifted sums are
+    never negative (|sum| <= 4 * 32768 * 255 < 128 << 18)."""
+    H, W, _ = a.shape
+    p = np.pad(a, ((0, H & 1), (0, W & 1), (0, 0)), mode="edge").astype(np.int64)
+    R, G, B = p[..., 0], p[..., 1], p[..., 2]
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    out = np.empty((Hc, Wc, 2), dtype=np.uint8)
+    for k, c in enumerate((-11059 * R - 21709 * G + 32768 * B, 32768 * R - 27439 * G - 5329 * B)):
+        s = c.reshape(Hc, 2, Wc, 2).sum(axis=(1, 3))
+        out[..., k] = np.clip((s + (128 << 18) + (1 << 17)) >> 18, 0, 255)
+    return np.ascontiguousarray(Y[:H, :W].astype(np.uint8)), out
+
+
+def _decode(job):
+    """``(H, W, record bytes as a flat uint8 array)`` of one file."""
     from PIL import Image
-    path, short_side = job
+    path, short_side, fmt = job
     with open(path, "rb") as fh:
         img = Image.open(fh)
         img.load()
@@ -68,16 +108,24 @@ def _decode(job) -> np.ndarray:
     size = shrunk_size(img.size[0], img.size[1], short_side)
     if size != img.size:
         img = img.resize(size, Image.BILINEAR)
-    return np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
+    a = np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
+    H, W, _ = a.shape
+    if fmt == "yuv420":
+        return H, W, np.concatenate([p.reshape(-1) for p in encode_yuv420(a)])
+    return H, W, a.reshape(-1)
 
 
 def write_packed(root: str, split: str, out_path: str, short_side: int = 256,
-                 workers: int = 0) -> dict:
+                 workers: int = 0, fmt: str = "rgb") -> dict:
     """Decode ``<root>/<split>/<class>/*`` with PIL and write the packed file ``out_path``
-    sequentially. ``workers`` > 0 decodes in that many processes (at most ``min(16, cpu_count)``).
-    Returns ``{"images", "classes", "pixel_bytes", "file_bytes"}``."""
+    sequentially. ``workers`` > 0 decodes (and encodes) in that many processes (at most
+    ``min(16, cpu_count)``). ``fmt`` "rgb" writes a version-1 file, "yuv420" a version-2 file of
+    half the pixel bytes (module docstring). Returns ``{"images", "classes", "pixel_bytes",
+    "file_bytes", "format"}``."""
     from ..ops.native_ops import AUG_MAX_SIDE
     from .folder import ImageFolder
+    if fmt not in FORMATS:
+        raise ValueError(f"fmt must be one of {sorted(FORMATS)}, got {fmt!r}")
     if short_side < 1:
         raise ValueError(f"short_side must be positive, got {short_side}")
     ds = ImageFolder(root, split)
@@ -87,7 +135,7 @@ def write_packed(root: str, split: str, out_path: str, short_side: int = 256,
     index_off = (names_off + len(names) + 7) // 8 * 8
     pixels_off = (index_off + N * 32 + 63) // 64 * 64
     index = np.zeros((N, 4), dtype="<i8")
-    jobs = [(path, short_side) for path, _ in ds.samples]
+    jobs = [(path, short_side, fmt) for path, _ in ds.samples]
     pool = None
     workers = min(int(workers), 16, os.cpu_count() or 1)
     if workers > 0:
@@ -100,15 +148,14 @@ def write_packed(root: str, split: str, out_path: str, short_side: int = 256,
         with open(out_path, "wb") as fh:
             fh.write(b"\0" * pixels_off)
             off = 0
-            for k, a in enumerate(decoded):
-                H, W, _ = a.shape
+            for k, (H, W, a) in enumerate(decoded):
                 if not (1 <= H <= AUG_MAX_SIDE and 1 <= W <= AUG_MAX_SIDE):
                     raise ValueError(f"{ds.samples[k][0]}: size {W}x{H} outside 1..{AUG_MAX_SIDE}")
                 index[k] = (off, H, W, ds.samples[k][1])
                 fh.write(a.tobytes())
                 off += a.size
             fh.seek(0)
-            fh.write(_HEADER.pack(MAGIC, VERSION, N, short_side, names_off, len(names), index_off,
+            fh.write(_HEADER.pack(MAGIC, FORMATS[fmt], N, short_side, names_off, len(names), index_off,
                                   pixels_off, off))
             fh.write(names)
             fh.seek(index_off)
@@ -117,7 +164,8 @@ def write_packed(root: str, split: str, out_path: str, short_side: int = 256,
         if pool is not None:
             pool.terminate()
             pool.join()
-    return {"images": N, "classes": len(ds.classes), "pixel_bytes": off, "file_bytes": pixels_off + off}
+    return {"images": N, "classes": len(ds.classes), "pixel_bytes": off, "file_bytes": pixels_off + off,
+            "format": fmt}
 
 
 class PackedImages:
@@ -137,8 +185,10 @@ class PackedImages:
             _HEADER.unpack_from(self._mm, 0)
         if magic != MAGIC:
             raise ValueError(f"{self.path}: bad magic {magic!r}, not a packed image file")
-        if version != VERSION:
-            raise ValueError(f"{self.path}: version {version}, this reader knows {VERSION}")
+        versions = {v: f for f, v in FORMATS.items()}
+        if version not in versions:
+            raise ValueError(f"{self.path}: version {version}, this reader knows {sorted(versions)}")
+        self.format = versions[version]
         if N < 1 or N >= 2 ** 31:
             raise ValueError(f"{self.path}: {N} records")
         if not (_HEADER.size <= names_off and names_off + names_len <= index_off and index_off % 8 == 0
@@ -162,7 +212,10 @@ class PackedImages:
             k = int(np.argmax(bad_size))
             raise ValueError(f"{self.path}: record {k}: size {int(W[k])}x{int(H[k])} outside "
                              f"1..{AUG_MAX_SIDE}")
-        nbytes = 3 * H * W                         # <= 3 * 2^30: no overflow
+        if self.format == "rgb":
+            nbytes = 3 * H * W                     # <= 3 * 2^30: no overflow
+        else:
+            nbytes = H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
         bad_off = (off < 0) | (off > pixels_len - nbytes)
         if bad_off.any():
             k = int(np.argmax(bad_off))
@@ -185,9 +238,22 @@ class PackedImages:
         return self.n
 
     def image(self, i: int) -> np.ndarray:
-        """HWC uint8 view of image ``i``."""
+        """HWC uint8 RGB view of image ``i`` of a version-1 file."""
+        if self.format != "rgb":
+            raise ValueError(f"{self.path}: a {self.format} file stores no RGB bytes; planes(i) "
+                             f"returns the stored Y and CbCr planes")
         off, H, W, _ = (int(v) for v in self.index[i])
         return self.pixels[off:off + 3 * H * W].reshape(H, W, 3)
+
+    def planes(self, i: int) -> Tuple[np.ndarray, np.ndarray]:
+        """``(Y [H, W], CbCr [Hc, Wc, 2])`` uint8 views of image ``i`` of a version-2 file."""
+        if self.format != "yuv420":
+            raise ValueError(f"{self.path}: a {self.format} file stores no planes; image(i) returns "
+                             f"the stored RGB bytes")
+        off, H, W, _ = (int(v) for v in self.index[i])
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        return (self.pixels[off:off + H * W].reshape(H, W),
+                self.pixels[off + H * W:off + H * W + 2 * Hc * Wc].reshape(Hc, Wc, 2))
 
     def label(self, i: int) -> int:
         return int(self.index[i, 3])
@@ -206,6 +272,7 @@ class PackedStore:
     def __init__(self, images: PackedImages, device, mode: str = "auto",
                  stage_bytes: int = STAGE_BYTES) -> None:
         self.images = images
+        self.format = images.format
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"packed images are resampled on the GPU (csrc/augment.hip); the device is "
@@ -217,11 +284,11 @@ class PackedStore:
         if mode == "auto":
             free, _ = torch.cuda.mem_get_info(self.device)
             mode = "device" if images.pixel_bytes <= free // 2 else "host"
-            print(f"packed data: {images.path}: {images.pixel_bytes} pixel bytes, {free} device bytes "
-                  f"free -> {mode} residency", flush=True)
+            print(f"packed data: {images.path}: {images.pixel_bytes} {images.format} pixel bytes, {free} "
+                  f"device bytes free -> {mode} residency", flush=True)
         else:
-            print(f"packed data: {images.path}: {images.pixel_bytes} pixel bytes -> {mode} residency "
-                  f"(requested)", flush=True)
+            print(f"packed data: {images.path}: {images.pixel_bytes} {images.format} pixel bytes -> {mode} "
+                  f"residency (requested)", flush=True)
         self.mode = mode
         self.index_dev = torch.from_numpy(np.array(images.index, dtype=np.int64)).to(self.device)
         self.pixels_dev: Optional[torch.Tensor] = None
@@ -337,7 +404,8 @@ class PackedLoader:
                                     self.resize, self.scale, self.ratio, batch_off=batch_off)
         shape = (B, S // 2, S // 2, 16) if self.layout == "s2d" else (B, 3, S, S)
         x = torch.empty(shape, dtype=self.dtype, device=self.device)
-        K.aug_resize_dev(packed, ti, tf, x, K.AUG_S2D if self.layout == "s2d" else K.AUG_NCHW)
+        K.aug_resize_dev(packed, ti, tf, x, K.AUG_S2D if self.layout == "s2d" else K.AUG_NCHW,
+                         K.AUG_YUV420 if self.store.format == "yuv420" else K.AUG_RGB)
         return x, labels
 
     def iter_from(self, start_step: int = 0) -> Iterator:

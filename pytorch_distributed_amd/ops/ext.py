@@ -120,6 +120,8 @@ _SIGS = {
     "pda_synth_s2d": [_V, _I, _U, _I, _V, _V, _I, _V, _I, _V],
     "pda_nchw_to_s2d": [_V, _I, _I, _I, _V, _I, _V],
     "pda_aug_resize": [_V, _V, _V, _I, _I, _V, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _V],
+    "pda_aug_resize_fmt": [_V, _V, _V, _I, _I, _V, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                           _V],
     "pda_aug_draw": [_V, _V, _V, _I, _L, _U, _I, _U, _I, _I, _I, _D, _D, _D, _D, _V, _V, _V, _V],
     "pda_pack_stem_s2d": [_V, _V, _I, _I, _V],
     "pda_stem_s2d_grad": [_V, _V, _I, _I, _V],

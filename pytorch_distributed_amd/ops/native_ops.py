@@ -28,7 +28,7 @@ __all__ = [
     "bn_apply", "stem_pool", "maxpool_bwd", "tail_pool", "bn_epilogue", "bn_bwd_finish",
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
-    "aug_draw", "aug_resize_dev",
+    "aug_draw", "aug_resize_dev", "aug_record_bytes",
 ]
 
 
@@ -1240,13 +1240,26 @@ def nchw_to_s2d(x, out) -> None:
 
 # ------------------------------------------------------------------ folder-image augmentation
 AUG_S2D, AUG_NCHW = 0, 1
+AUG_RGB, AUG_YUV420 = 0, 1          # source record format: HWC RGB | Y plane + half-resolution CbCr
 AUG_MAX_SIDE = 32768
 
 
-def aug_check(packed, table_i64, table_f64, out, layout: int) -> Tuple[int, int]:
+def aug_record_bytes(H: int, W: int, fmt: int) -> int:
+    """Bytes of one HxW source record: ``3*H*W`` (RGB) or ``H*W + 2*Hc*Wc`` with ``Hc = (H+1)//2``,
+    ``Wc = (W+1)//2`` (YCbCr 4:2:0)."""
+    if fmt == AUG_RGB:
+        return 3 * H * W
+    if fmt == AUG_YUV420:
+        return H * W + 2 * ((H + 1) // 2) * ((W + 1) // 2)
+    raise ValueError(f"aug_resize: fmt must be {AUG_RGB} (rgb) or {AUG_YUV420} (yuv420), got {fmt!r}")
+
+
+def aug_check(packed, table_i64, table_f64, out, layout: int, fmt: int = AUG_RGB) -> Tuple[int, int]:
     """Host-side validation of an :func:`aug_resize` call; returns (B, S). Pure Python on host
     tensors (the kernel library is not loaded), and run before anything is launched: the kernel
-    (csrc/augment.hip) trusts every offset, size and box it is given."""
+    (csrc/augment.hip) trusts every offset, size and box it is given. Each image is bounded by the
+    record size of ``fmt`` (:func:`aug_record_bytes`)."""
+    aug_record_bytes(1, 1, fmt)
     if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
         raise ValueError("aug_resize: packed must be a contiguous 1-D uint8 tensor")
     for name, t, dt in (("table_i64", table_i64, torch.int64), ("table_f64", table_f64, torch.float64)):
@@ -1281,8 +1294,9 @@ def aug_check(packed, table_i64, table_f64, out, layout: int) -> Tuple[int, int]
     for b, ((off, H, W, _), box) in enumerate(zip(table_i64.tolist(), table_f64.tolist())):
         if not (1 <= H <= AUG_MAX_SIDE and 1 <= W <= AUG_MAX_SIDE):
             raise ValueError(f"aug_resize: image {b}: size {W}x{H} outside 1..{AUG_MAX_SIDE}")
-        if off < 0 or off + H * W * 3 > n:
-            raise ValueError(f"aug_resize: image {b}: bytes [{off}, {off + H * W * 3}) outside the "
+        m = aug_record_bytes(H, W, fmt)
+        if off < 0 or off + m > n:
+            raise ValueError(f"aug_resize: image {b}: bytes [{off}, {off + m}) outside the "
                              f"packed buffer of {n}")
         x0, y0, x1, y1 = box
         if not all(math.isfinite(v) for v in box):
@@ -1292,13 +1306,15 @@ def aug_check(packed, table_i64, table_f64, out, layout: int) -> Tuple[int, int]
     return B, S
 
 
-def aug_resize(packed, table_i64, table_f64, out, layout: int = AUG_S2D) -> None:
-    """Resample / flip / normalise a packed batch of raw uint8 HWC images into ``out`` (one launch,
+def aug_resize(packed, table_i64, table_f64, out, layout: int = AUG_S2D, fmt: int = AUG_RGB) -> None:
+    """Resample / flip / normalise a packed batch of raw uint8 images into ``out`` (one launch,
     csrc/augment.hip). ``packed``: device bytes; ``table_i64`` [B,4] = byte offset, H, W, flip and
     ``table_f64`` [B,4] = box x0, y0, x1, y1: HOST tensors (pinned ones upload asynchronously),
-    validated by :func:`aug_check` before the launch."""
+    validated by :func:`aug_check` before the launch. ``fmt``: the records are HWC RGB
+    (``AUG_RGB``) or a Y plane followed by the interleaved half-resolution CbCr plane
+    (``AUG_YUV420``, decoded inside the kernel)."""
     from ..data.synthetic import MEAN, STD
-    B, S = aug_check(packed, table_i64, table_f64, out, layout)
+    B, S = aug_check(packed, table_i64, table_f64, out, layout, fmt)
     if packed.device.type != "cuda":
         raise ValueError("aug_resize runs on a GPU; the packed images are on " + str(packed.device))
     if out.data_ptr() % 16:
@@ -1306,8 +1322,8 @@ def aug_resize(packed, table_i64, table_f64, out, layout: int = AUG_S2D) -> None
     ti = table_i64.to(packed.device, non_blocking=True)
     tf = table_f64.to(packed.device, non_blocking=True)
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
-    check(ext.lib().pda_aug_resize(ptr(packed), ptr(ti), ptr(tf), B, S, ptr(out), dt_of(out), layout,
-                                   mean, std, stream(out.device)), "aug_resize")
+    check(ext.lib().pda_aug_resize_fmt(ptr(packed), ptr(ti), ptr(tf), B, S, ptr(out), dt_of(out), layout,
+                                       fmt, mean, std, stream(out.device)), "aug_resize")
 
 
 AUG_TRAIN, AUG_VAL = 0, 1
@@ -1365,10 +1381,12 @@ def aug_draw(ids, index_dev, N: int, seed: int, split: str, epoch: int, mode: in
     return ti, tf, labels
 
 
-def aug_resize_dev(packed, ti_dev, tf_dev, out, layout: int = AUG_S2D) -> None:
+def aug_resize_dev(packed, ti_dev, tf_dev, out, layout: int = AUG_S2D, fmt: int = AUG_RGB) -> None:
     """:func:`aug_resize` on DEVICE tables that :func:`aug_draw` wrote from a validated index (the
-    kernel trusts them; nothing is read back): resample / flip / normalise into ``out``."""
+    kernel trusts them; nothing is read back): resample / flip / normalise into ``out``. ``fmt`` is
+    the record format the index was validated for."""
     from ..data.synthetic import MEAN, STD
+    aug_record_bytes(1, 1, fmt)
     if packed.device.type != "cuda":
         raise ValueError("aug_resize_dev runs on a GPU; the packed images are on " + str(packed.device))
     if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
@@ -1393,8 +1411,8 @@ def aug_resize_dev(packed, ti_dev, tf_dev, out, layout: int = AUG_S2D) -> None:
         raise ValueError(f"aug_resize_dev: output {tuple(out.shape)} {out.dtype} does not fit layout "
                          f"{layout} for {B} images (even S >= 2, contiguous, 16-byte aligned)")
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
-    check(ext.lib().pda_aug_resize(ptr(packed), ptr(ti_dev), ptr(tf_dev), B, S, ptr(out), dt_of(out),
-                                   layout, mean, std, stream(out.device)), "aug_resize_dev")
+    check(ext.lib().pda_aug_resize_fmt(ptr(packed), ptr(ti_dev), ptr(tf_dev), B, S, ptr(out), dt_of(out),
+                                       layout, fmt, mean, std, stream(out.device)), "aug_resize_dev")
 
 
 def pack_stem_s2d(src_ohwi, dst) -> None:
