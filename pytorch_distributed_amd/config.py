@@ -50,6 +50,9 @@ class RunConfig:
     graph: bool = False              # single-GPU native engine: replay each step from a HIP graph
     aug: str = "cpu"                 # folder data: cpu (PIL in the workers) | gpu (csrc/augment.hip)
     pack_resident: str = "auto"      # packed data: auto | device (pixels in HBM) | host (per-batch upload)
+    nesterov: bool = False           # Nesterov momentum
+    no_bn_decay: bool = False        # no weight decay on 1-D parameters (BatchNorm weight / bias, fc bias)
+    lars: float = 0.0                # LARS trust coefficient on conv / fc weights (0 = off)
 
     def replace(self, **kw) -> "RunConfig":
         return dataclasses.replace(self, **kw)
@@ -61,6 +64,11 @@ SCRIPT_DEFAULTS = {
     "ddp": dict(batch_size=400, save_path="output/resnet_ddp"),
     "ddp_amp": dict(batch_size=400, save_path="output/resnet_ddp_amp", dtype="fp16"),
 }
+
+
+def _bool(s: str) -> bool:
+    return s not in ("", "0", "false", "False")
+
 
 _ENV = {
     "MX_EPOCHS": ("epochs", int),
@@ -88,6 +96,9 @@ _ENV = {
     "MX_GRAPH": ("graph", lambda s: s not in ("", "0", "false", "False")),
     "MX_AUG": ("aug", str),
     "MX_PACK_RESIDENT": ("pack_resident", str),
+    "MX_NESTEROV": ("nesterov", _bool),
+    "MX_NO_BN_DECAY": ("no_bn_decay", _bool),
+    "MX_LARS": ("lars", float),
 }
 
 
@@ -130,6 +141,10 @@ def config_for(script: str, env: Optional[dict] = None,
         raise ValueError(f"MX_AUG must be cpu|gpu, got {cfg.aug!r}")
     if cfg.pack_resident not in ("auto", "device", "host"):
         raise ValueError(f"MX_PACK_RESIDENT must be auto|device|host, got {cfg.pack_resident!r}")
+    if not cfg.lars >= 0 or cfg.lars == float("inf"):
+        raise ValueError(f"MX_LARS is a trust coefficient >= 0 (0 = off), got {cfg.lars!r}")
+    if cfg.nesterov and not cfg.momentum > 0:
+        raise ValueError("MX_NESTEROV needs momentum > 0")
     if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:
         raise ValueError("MX_DATA=packed:<dir> needs the directory that holds train.pack and val.pack")
     return cfg

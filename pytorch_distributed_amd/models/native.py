@@ -1217,8 +1217,10 @@ class NativeResNet(nn.Module):
         with torch.no_grad():
             return self.native_forward(x, train=train, save=False)
 
-    def make_optimizer(self, lr=0.1, momentum=0.9, weight_decay=1e-4) -> "NativeSGD":
-        return NativeSGD(self, lr=lr, momentum=momentum, weight_decay=weight_decay)
+    def make_optimizer(self, lr=0.1, momentum=0.9, weight_decay=1e-4, nesterov=False, lars=0.0,
+                       lars_eps=1e-8, param_groups=None) -> "NativeSGD":
+        return NativeSGD(self, lr=lr, momentum=momentum, weight_decay=weight_decay,
+                         nesterov=nesterov, lars=lars, lars_eps=lars_eps, param_groups=param_groups)
 
     def make_criterion(self) -> "NativeCrossEntropy":
         return NativeCrossEntropy(self)
@@ -1302,16 +1304,42 @@ class NativeSGD(torch.optim.Optimizer):
     """torch.optim.SGD semantics (momentum, dampening 0, weight decay on every parameter -- as the
     reference, quirk Q12) executed as ONE fused kernel over the flat buffers, which also refreshes
     the 16-bit weight shadow. ``state_dict()`` has torch SGD's format (per-parameter
-    ``momentum_buffer``), so checkpoints interchange with the reference's optimizer."""
+    ``momentum_buffer``), so checkpoints interchange with the reference's optimizer.
+
+    ``param_groups`` (torch-style group dicts: ``params`` plus any of ``lr``, ``momentum``,
+    ``weight_decay``, ``nesterov``, ``lars``, ``lars_eps``; the constructor arguments are the
+    defaults), ``nesterov=True`` or a trust coefficient ``lars > 0`` select the *segmented* step
+    (``self.segmented``): one ``sgd_seg`` launch (``csrc/optim.hip``) that reads each parameter
+    tensor's hyper-parameters from a device table, after a ``seg_norms`` launch when some group has a
+    trust coefficient. Parameters given to no group are frozen: their master weights, momentum and
+    shadow are never touched. The groups' hyper-parameters may change between steps (``StepLR``); the
+    table is re-uploaded when they do. Without these arguments the optimizer is the one-launch
+    ``sgd_flat`` step, unchanged."""
+
+    @staticmethod
+    def wants_segments(param_groups=None, nesterov=False, lars=0.0, **_kw) -> bool:
+        """Whether these constructor arguments select the segmented step."""
+        return param_groups is not None or bool(nesterov) or lars != 0
 
     def __init__(self, model: NativeResNet, lr=0.1, momentum=0.9, weight_decay=1e-4,
-                 dampening=0.0, nesterov=False) -> None:
-        if dampening != 0.0 or nesterov:
-            raise ValueError("NativeSGD implements dampening=0, nesterov=False (reference settings)")
+                 dampening=0.0, nesterov=False, lars=0.0, lars_eps=1e-8, param_groups=None) -> None:
+        self._sealed = False
+        self.segmented = self.wants_segments(param_groups, nesterov, lars)
+        if dampening != 0.0:
+            raise ValueError("NativeSGD implements dampening=0 (reference setting)")
         defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
                         nesterov=False, maximize=False, foreach=None, differentiable=False,
                         fused=None)
-        super().__init__(list(model.parameters()), defaults)
+        if self.segmented:
+            from ..optim import normalize_param_groups
+            defaults.update(nesterov=bool(nesterov), lars=lars, lars_eps=lars_eps)
+            groups = normalize_param_groups(list(model.parameters()), param_groups, defaults)
+            if not any(g["params"] for g in groups):
+                raise ValueError("NativeSGD: the parameter groups hold no parameter")
+            super().__init__(groups, defaults)
+        else:
+            super().__init__(list(model.parameters()), defaults)
+        self._sealed = True
         self.model = model
         self.flat_mom = torch.zeros_like(model.flat_params)
         self._initialized = False
@@ -1319,18 +1347,53 @@ class NativeSGD(torch.optim.Optimizer):
         self._views = {}
         fp = model.flat_params
         base = fp.data_ptr()
-        for p in self.param_groups[0]["params"]:
-            off = (p.data_ptr() - base) // 4
-            v = self.flat_mom[off:off + p.numel()]
-            if p.dim() == 4:
-                O, I, R, S_ = p.shape
-                v = v.view(O, R, S_, I).permute(0, 3, 1, 2)
-            else:
-                v = v.view(p.shape)
-            self._views[p] = v
+        segments = []
+        for g in self.param_groups:
+            for p in g["params"]:
+                off = (p.data_ptr() - base) // 4
+                segments.append((off, p.numel()))
+                v = self.flat_mom[off:off + p.numel()]
+                if p.dim() == 4:
+                    O, I, R, S_ = p.shape
+                    v = v.view(O, R, S_, I).permute(0, 3, 1, 2)
+                else:
+                    v = v.view(p.shape)
+                self._views[p] = v
+        if self.segmented:
+            # one segment per parameter tensor (the fc weight: its num_classes rows, not the padded
+            # ones), in group order; the device table is built once and re-uploaded on a change
+            self._uploaded = self._hyper_rows()
+            self._tables, _ = K.seg_tables(segments, self._uploaded, fp.device)
+
+    def add_param_group(self, param_group) -> None:
+        if getattr(self, "_sealed", False):
+            raise ValueError("NativeSGD: the groups are fixed at construction (the segment table is "
+                             "built once); pass param_groups to the constructor")
+        super().add_param_group(param_group)
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         self.model.zero_grad_flat()
+
+    def _hyper_rows(self) -> list:
+        """One hyper-parameter row per segment, from the groups as they are now."""
+        from ..optim import GROUP_KEYS, check_hyper
+        rows = []
+        for i, g in enumerate(self.param_groups):
+            h = {k: g[k] for k in GROUP_KEYS}
+            check_hyper(h, f"NativeSGD: param_groups[{i}]: ")
+            rows += [h] * len(g["params"])
+        return rows
+
+    def _launch_segments(self, inv_scale=None, found_inf=None) -> None:
+        m = self.model
+        rows = self._hyper_rows()
+        if rows != self._uploaded:      # a scheduler (or the user) edited a group since the last step
+            self._tables.set_hyper(rows)
+            self._uploaded = rows
+        if self._tables.any_trust:
+            K.seg_norms(m.flat_params, m.flat_grad, self._tables)
+        K.sgd_seg(m.flat_params, m.flat_grad, self.flat_mom, None if m.f32 else m.flat_shadow,
+                  self._tables, self._initialized, inv_scale=inv_scale, found_inf=found_inf)
 
     def _launch_range(self, lo: int, hi: int, inv_scale=None, found_inf=None) -> None:
         g = self.param_groups[0]
@@ -1347,13 +1410,17 @@ class NativeSGD(torch.optim.Optimizer):
             # and SGD skips parameters without a gradient -- the flat gradient still holds the
             # previous step's values (no memset), so applying it would be a stale update
             return
-        self._launch_range(0, m.numel, inv_scale, found_inf)
+        if self.segmented:
+            self._launch_segments(inv_scale, found_inf)
+        else:
+            self._launch_range(0, m.numel, inv_scale, found_inf)
         m._pack_stem()
         # (an overflow-skipped first step leaves the momentum buffer unset on the device but the
         # flag set: the next step then reads the zero-initialised buffer, m*0 + d == d)
         self._initialized = True
-        for p in g["params"]:
-            self.state[p]["momentum_buffer"] = self._views[p]
+        for g in self.param_groups:
+            for p in g["params"]:
+                self.state[p]["momentum_buffer"] = self._views[p]
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -1382,15 +1449,21 @@ class NativeSGD(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        if self.segmented:
+            # a checkpoint of a plain torch.optim.SGD carries no lars / lars_eps: keep the defaults
+            for g in self.param_groups:
+                for k, v in self.defaults.items():
+                    g.setdefault(k, v)
         with torch.no_grad():
             any_buf = False
-            for p in self.param_groups[0]["params"]:
-                st = self.state.get(p, {})
-                buf = st.get("momentum_buffer")
-                if buf is not None:
-                    self._views[p].copy_(buf)
-                    st["momentum_buffer"] = self._views[p]
-                    any_buf = True
+            for g in self.param_groups:
+                for p in g["params"]:
+                    st = self.state.get(p, {})
+                    buf = st.get("momentum_buffer")
+                    if buf is not None:
+                        self._views[p].copy_(buf)
+                        st["momentum_buffer"] = self._views[p]
+                        any_buf = True
             self._initialized = any_buf
 
 

@@ -135,6 +135,10 @@ _SIGS = {
     "pda_event_destroy": [_V],
     "pda_stream_wait_event": [_V, _V],
     "pda_bn_bwd_apply2": [_V, _V, _V, _V, _V, _V, _L, _I, _I, _V],
+    "pda_seg_check": [_V, _I, _V, _I, _L],
+    "pda_seg_chunk": [],
+    "pda_seg_norms": [_V, _V, _L, _V, _V, _V, _V, _I, _I, _V, _V],
+    "pda_sgd_seg": [_V, _V, _V, _V, _L, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _V],
 }
 
 

@@ -29,6 +29,7 @@ __all__ = [
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
     "aug_draw", "aug_resize_dev", "aug_record_bytes",
+    "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg",
 ]
 
 
@@ -1199,6 +1200,153 @@ def amp_scan(g, found_inf, inv_scale, scale, tracker, ws, growth=2.0, backoff=0.
     check(ext.lib().pda_amp_scan(ptr(g), g.numel(), ptr(found_inf), ptr(inv_scale), ptr(scale),
                                  ptr(tracker), ptr(ws), float(growth), float(backoff), int(interval),
                                  stream(g.device)), "amp_scan")
+
+
+# ------------------------------------------------------------------ segmented optimizer (csrc/optim.hip)
+SEG_CHUNK = 4096      # elements one block of seg_norms / sgd_seg handles (csrc/optim.hip SEG_CHUNK)
+SEG_NESTEROV = 1      # SegRow.flags
+
+
+class SegRow(C.Structure):
+    """One parameter tensor's range of the flat buffers and its hyper-parameters (csrc/optim.hip)."""
+    _fields_ = [("off", C.c_longlong), ("numel", C.c_longlong), ("lr", C.c_float),
+                ("momentum", C.c_float), ("wd", C.c_float), ("trust", C.c_float), ("eps", C.c_float),
+                ("flags", C.c_int), ("blk0", C.c_int), ("nblk", C.c_int)]
+
+
+class BlkRow(C.Structure):
+    """One block's chunk: ``count`` <= SEG_CHUNK elements of segment ``seg`` from flat index ``first``."""
+    _fields_ = [("first", C.c_longlong), ("seg", C.c_int), ("count", C.c_int)]
+
+
+_SEG_ERRORS = {-1: "bad counts or a missing buffer", -2: "a segment offset is negative or no multiple of 4",
+               -3: "a segment is empty or ends past the flat buffer", -4: "segments overlap",
+               -5: "a hyper-parameter is negative or not finite",
+               -6: "the block table does not cover every segment exactly once in chunks of at most "
+                   "SEG_CHUNK elements"}
+_SEG_HYPER = ("lr", "momentum", "weight_decay", "lars", "lars_eps", "nesterov")
+
+
+class SegTables:
+    """Segment and block tables of the segmented optimizer: host rows (ctypes arrays, validated by the
+    launchers before every launch) and their device copies (what the kernels read)."""
+
+    def __init__(self, seg_host, blk_host, device) -> None:
+        self.seg_host, self.blk_host = seg_host, blk_host
+        self.nseg, self.nblocks = len(seg_host), len(blk_host)
+        self.device = self.seg_dev = self.blk_dev = None    # device=None: host rows only
+        if device is not None:
+            self.device = torch.device(device)
+            self.seg_dev = self._upload(seg_host)
+            self.blk_dev = self._upload(blk_host)
+            self.device = self.seg_dev.device     # with its index
+        self.slab = None    # 2 doubles per block, allocated when a trust coefficient first needs it
+        self.any_trust = any(r.trust > 0 for r in seg_host)   # seg_norms runs only then
+
+    def _upload(self, rows) -> torch.Tensor:
+        if len(rows) == 0:
+            return torch.zeros(16, dtype=torch.uint8, device=self.device)
+        return torch.frombuffer(rows, dtype=torch.uint8).to(self.device)
+
+    def set_hyper(self, hyper) -> None:
+        """New hyper-parameters for every segment: the host rows are rewritten and uploaded in stream
+        order (a copy from pageable memory returns once the rows are staged)."""
+        if len(hyper) != self.nseg:
+            raise ValueError(f"seg_tables: {len(hyper)} hyper-parameter rows for {self.nseg} segments")
+        for r, h in zip(self.seg_host, hyper):
+            _fill_hyper(r, h)
+        self.any_trust = any(r.trust > 0 for r in self.seg_host)
+        if self.nseg and self.seg_dev is not None:
+            self.seg_dev.copy_(torch.frombuffer(self.seg_host, dtype=torch.uint8))
+
+
+def _fill_hyper(r: SegRow, h) -> None:
+    unknown = set(h) - set(_SEG_HYPER)
+    if unknown:
+        raise ValueError(f"seg_tables: unknown hyper-parameter(s) {sorted(unknown)}")
+    r.lr, r.momentum = float(h["lr"]), float(h.get("momentum", 0.0))
+    r.wd, r.trust = float(h.get("weight_decay", 0.0)), float(h.get("lars", 0.0))
+    r.eps = float(h.get("lars_eps", 1e-8))
+    r.flags = SEG_NESTEROV if h.get("nesterov", False) else 0
+
+
+def seg_tables(segments, hyper, device="cuda") -> Tuple[SegTables, int]:
+    """Device tables of the segmented optimizer. ``segments``: one ``(offset, numel)`` per parameter
+    tensor (elements of the flat buffer); ``hyper``: one dict per segment with ``lr`` and optionally
+    ``momentum``, ``weight_decay``, ``nesterov``, ``lars`` (trust coefficient, 0 = off), ``lars_eps``.
+    Every segment is cut into chunks of SEG_CHUNK elements, one block each. Returns (tables, number
+    of blocks); the launchers validate the tables against the buffers they are launched on."""
+    segments = [(int(o), int(n)) for o, n in segments]
+    if len(segments) != len(hyper):
+        raise ValueError(f"seg_tables: {len(hyper)} hyper-parameter rows for {len(segments)} segments")
+    nblk = sum(max((n + SEG_CHUNK - 1) // SEG_CHUNK, 0) for _, n in segments)
+    if nblk >= 2 ** 31:
+        raise ValueError("seg_tables: more than 2^31 - 1 blocks")
+    segs, blks = (SegRow * len(segments))(), (BlkRow * nblk)()
+    b = 0
+    for i, ((off, n), h) in enumerate(zip(segments, hyper)):
+        r = segs[i]
+        r.off, r.numel, r.blk0 = off, n, b
+        _fill_hyper(r, h)
+        for first in range(off, off + n, SEG_CHUNK):
+            blks[b].first, blks[b].seg, blks[b].count = first, i, min(SEG_CHUNK, off + n - first)
+            b += 1
+        r.nblk = b - r.blk0
+    return SegTables(segs, blks, device), nblk
+
+
+def _seg_check(rc: int, what: str) -> None:
+    if rc < 0:
+        raise ValueError(f"{what}: {_SEG_ERRORS.get(rc, f'bad tables ({rc})')}")
+    check(rc, what)
+
+
+def _seg_flat(what: str, n: int, dev, **ts) -> None:
+    if dev is None or dev.type != "cuda":
+        raise ValueError(f"{what} runs on a GPU; the tables are on {dev}")
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if t.device != dev or not t.is_contiguous() or t.numel() != n or t.data_ptr() % 16:
+            raise ValueError(f"{what}: {name} must be a contiguous, 16-byte aligned tensor of {n} "
+                             f"elements on {dev}")
+
+
+def seg_norms(p, g, tables: SegTables) -> None:
+    """Per-block sums of p^2 and g^2 (double) of every segment with a trust coefficient, into
+    ``tables.slab``; :func:`sgd_seg` turns them into the LARS trust ratios."""
+    _seg_flat("seg_norms", p.numel(), tables.device, p=p, g=g)
+    if p.dtype != torch.float32 or g.dtype != torch.float32:
+        raise ValueError("seg_norms: p and g are f32")
+    if tables.slab is None or tables.slab.numel() < 2 * tables.nblocks:
+        tables.slab = torch.zeros(max(2 * tables.nblocks, 2), dtype=torch.float64, device=tables.device)
+    rc = ext.lib().pda_seg_norms(ptr(p), ptr(g), p.numel(), ptr(tables.seg_dev), ptr(tables.blk_dev),
+                                 C.cast(tables.seg_host, C.c_void_p), C.cast(tables.blk_host, C.c_void_p),
+                                 tables.nseg, tables.nblocks, ptr(tables.slab), stream(p.device))
+    _seg_check(rc, "seg_norms")
+
+
+def sgd_seg(p, g, buf, shadow, tables: SegTables, initialized: bool, inv_scale=None,
+            found_inf=None) -> None:
+    """SGD over the segments of ``tables`` (per-segment lr, momentum, weight decay, Nesterov and LARS
+    trust ratio); ``inv_scale`` / ``found_inf`` as in :func:`sgd_flat`. Segments with a trust
+    coefficient read the norms of a preceding :func:`seg_norms`. Elements in no segment stay."""
+    n = p.numel()
+    _seg_flat("sgd_seg", n, tables.device, p=p, g=g, buf=buf, shadow=shadow)
+    if any(t.dtype != torch.float32 for t in (p, g, buf)):
+        raise ValueError("sgd_seg: p, g and buf are f32")
+    if shadow is not None and shadow.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError("sgd_seg: the shadow is bf16 or fp16")
+    if tables.any_trust and tables.slab is None:
+        raise ValueError("sgd_seg: a trust coefficient needs seg_norms before the update")
+    flags = (1 if initialized else 0) | (2 if shadow is not None else 0)
+    dt = dt_of(shadow) if shadow is not None else 1
+    rc = ext.lib().pda_sgd_seg(ptr(p), ptr(g), ptr(buf), ptr(shadow), n, ptr(tables.seg_dev),
+                               ptr(tables.blk_dev), C.cast(tables.seg_host, C.c_void_p),
+                               C.cast(tables.blk_host, C.c_void_p), tables.nseg, tables.nblocks,
+                               ptr(tables.slab), ptr(inv_scale), ptr(found_inf), flags, dt,
+                               stream(p.device))
+    _seg_check(rc, "sgd_seg")
 
 
 def pack_stem(src_ohwi, dst, Cout=64, RS=49, Cin=3, Cpad=8) -> None:

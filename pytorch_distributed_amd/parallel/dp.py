@@ -163,11 +163,27 @@ class DataParallel(nn.Module):
         return [self.module] + self.replicas
 
     # ------------------------------------------------------------------ factories
+    def _refuse_segmented(self, segmented: bool) -> None:
+        """The replica-graph path (several devices, or PDA_DP_FORCE_REPLAY=1 on one) takes no
+        segmented optimizer; one device runs the module's own eager step and does."""
+        if segmented and self._native and (self.replicas or self.force_replay):
+            from ..runtime.graphs import SEGMENTED_REFUSAL
+            raise ValueError(SEGMENTED_REFUSAL.format(
+                what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+
     def make_optimizer(self, **kw):
         if self._native:
+            from ..models.native import NativeSGD
+            self._refuse_segmented(NativeSGD.wants_segments(**kw))
             opts = [m.make_optimizer(**kw) for m in self.all_modules]
             return ReplicatedSGD(opts) if self.replicas else opts[0]
-        return torch.optim.SGD(self.module.parameters(), **kw)
+        groups = kw.pop("param_groups", None)
+        params = groups if groups is not None else self.module.parameters()
+        if kw.get("lars", 0) > 0 or any(g.get("lars", 0) > 0 for g in groups or []):
+            from ..optim import LARS
+            return LARS(params, **kw)
+        kw.pop("lars", None), kw.pop("lars_eps", None)
+        return torch.optim.SGD(params, **kw)
 
     def make_criterion(self):
         if not self.replicas and hasattr(self.module, "make_criterion"):
@@ -302,6 +318,7 @@ class DataParallel(nn.Module):
     def train_step_chunks(self, xs, ys, optimizer, graph: bool = True) -> torch.Tensor:
         """:meth:`train_step` on per-replica input chunks (e.g. generated on each GPU directly,
         skipping the scatter from ``device_ids[0]``)."""
+        self._refuse_segmented(getattr(optimizer, "segmented", False))
         if graph and not self.replicas and not self.force_replay:
             # one device: the module's own (eager, two-stream) step, as torch's DataParallel calls
             # the module directly for a single device; replay only pays where one host thread

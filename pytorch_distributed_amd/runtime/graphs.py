@@ -132,6 +132,17 @@ def graphs_unsafe_warning(what: str) -> None:
                   "launching eagerly", RuntimeWarning)
 
 
+# Captured steps bake the learning rate into the optimizer launch and re-capture when it changes;
+# the segmented optimizer (parameter groups, Nesterov, LARS: models/native.py NativeSGD.segmented)
+# keeps its hyper-parameters in a device table that is re-uploaded between steps, which a replayed
+# graph would not see. It is refused there, with no fall-back to eager launches.
+SEGMENTED_REFUSAL = ("{what} cannot run the segmented optimizer (parameter groups, Nesterov or LARS): "
+                     "captured steps (MX_GRAPH=1, the DataParallel replica graphs) take their "
+                     "hyper-parameters at capture. Run without MX_GRAPH / on one device without "
+                     "DataParallel's replay (the single-GPU and DDP scripts work), or drop "
+                     "MX_NESTEROV / MX_NO_BN_DECAY / MX_LARS / param_groups")
+
+
 class GraphedNativeStep:
     """Capture-once / replay-per-step driver of :func:`native_train_step`.
 
@@ -143,6 +154,8 @@ class GraphedNativeStep:
 
     def __init__(self, model, opt, gen: Callable, batch: int, scaler=None,
                  device: Optional[torch.device] = None) -> None:
+        if getattr(opt, "segmented", False):
+            raise ValueError(SEGMENTED_REFUSAL.format(what="GraphedNativeStep (MX_GRAPH=1)"))
         self.model, self.opt, self.gen, self.batch, self.scaler = model, opt, gen, batch, scaler
         self.device = torch.device(device) if device is not None else model.device
         self.ids_base = torch.arange(batch, dtype=torch.int64, device=self.device)

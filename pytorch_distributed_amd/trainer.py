@@ -328,11 +328,29 @@ def _factory_owner(model: nn.Module, attr: str):
 
 
 def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
+    """SGD as the reference builds it; ``MX_NESTEROV`` / ``MX_NO_BN_DECAY`` / ``MX_LARS`` turn it into
+    grouped SGD (:func:`~pytorch_distributed_amd.optim.build_param_groups`): the segmented kernel on
+    the native engine, ``torch.optim.SGD`` or :class:`~pytorch_distributed_amd.optim.LARS` on the
+    torch engine. The captured-step paths refuse the segmented optimizer (ValueError, raised here:
+    before training starts)."""
     inner = _factory_owner(model, "make_optimizer")
-    if hasattr(inner, "make_optimizer"):
-        return inner.make_optimizer(lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay)
-    return torch.optim.SGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
-                           weight_decay=cfg.weight_decay)
+    native = hasattr(inner, "make_optimizer")
+    if not (cfg.nesterov or cfg.no_bn_decay or cfg.lars > 0):
+        if native:
+            return inner.make_optimizer(lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay)
+        return torch.optim.SGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
+                               weight_decay=cfg.weight_decay)
+    from .optim import LARS, build_param_groups
+    if native and cfg.graph and ctx.engine == "native":
+        from .runtime.graphs import SEGMENTED_REFUSAL
+        raise ValueError(SEGMENTED_REFUSAL.format(what="MX_GRAPH=1"))
+    groups = build_param_groups(_unwrap(model), cfg.weight_decay, cfg.no_bn_decay, cfg.lars)
+    kw = dict(lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay, nesterov=cfg.nesterov)
+    if native:      # (DataParallel over several devices raises the same ValueError)
+        return inner.make_optimizer(param_groups=groups, **kw)
+    if cfg.lars > 0:
+        return LARS(groups, **kw)
+    return torch.optim.SGD(groups, **kw)
 
 
 def build_criterion(ctx: Context, model: nn.Module):
