@@ -53,6 +53,14 @@ class RunConfig:
     nesterov: bool = False           # Nesterov momentum
     no_bn_decay: bool = False        # no weight decay on 1-D parameters (BatchNorm weight / bias, fc bias)
     lars: float = 0.0                # LARS trust coefficient on conv / fc weights (0 = off)
+    label_smoothing: float = 0.0     # cross-entropy label smoothing eps in [0, 1)
+    mixup: float = 0.0               # mixup Beta(alpha, alpha) (0 = off)
+    cutmix: float = 0.0              # CutMix Beta(alpha, alpha) (0 = off)
+
+    @property
+    def soft_targets(self) -> bool:
+        """Label smoothing, mixup or CutMix is on: the loss takes soft targets."""
+        return self.label_smoothing > 0 or self.mixup > 0 or self.cutmix > 0
 
     def replace(self, **kw) -> "RunConfig":
         return dataclasses.replace(self, **kw)
@@ -99,6 +107,9 @@ _ENV = {
     "MX_NESTEROV": ("nesterov", _bool),
     "MX_NO_BN_DECAY": ("no_bn_decay", _bool),
     "MX_LARS": ("lars", float),
+    "MX_LABEL_SMOOTHING": ("label_smoothing", float),
+    "MX_MIXUP": ("mixup", float),
+    "MX_CUTMIX": ("cutmix", float),
 }
 
 
@@ -143,6 +154,12 @@ def config_for(script: str, env: Optional[dict] = None,
         raise ValueError(f"MX_PACK_RESIDENT must be auto|device|host, got {cfg.pack_resident!r}")
     if not cfg.lars >= 0 or cfg.lars == float("inf"):
         raise ValueError(f"MX_LARS is a trust coefficient >= 0 (0 = off), got {cfg.lars!r}")
+    if not 0 <= cfg.label_smoothing < 1:
+        raise ValueError(f"MX_LABEL_SMOOTHING is a smoothing weight in [0, 1) (0 = off), got "
+                         f"{cfg.label_smoothing!r}")
+    for var, v in (("MX_MIXUP", cfg.mixup), ("MX_CUTMIX", cfg.cutmix)):
+        if not v >= 0 or v == float("inf"):
+            raise ValueError(f"{var} is a Beta(alpha, alpha) parameter >= 0 (0 = off), got {v!r}")
     if cfg.nesterov and not cfg.momentum > 0:
         raise ValueError("MX_NESTEROV needs momentum > 0")
     if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:

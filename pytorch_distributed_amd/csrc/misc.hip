@@ -430,6 +430,12 @@ int pda_xent(const float* logits, int B, int K, int ld_in, const long long* labe
   return (int)hipGetLastError();
 }
 
+// loss = mean(loss_rows) alone: the second launch of pda_xent, for the soft-target loss (mix.hip)
+int pda_mean_rows(const float* v, int n, float* out, hipStream_t st) {
+  TRACKED_LAUNCH(mean_kernel, dim3(1), dim3(1024), 0, st, v, n, out);
+  return (int)hipGetLastError();
+}
+
 int pda_topk(const float* logits, int B, int K, int ld, const long long* labels, float* hits,
              hipStream_t st) {
   TRACKED_LAUNCH(topk_kernel, dim3((B + 3) / 4), dim3(NT), 0, st, logits, B, K, ld, labels, hits);

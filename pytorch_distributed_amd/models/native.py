@@ -1222,8 +1222,8 @@ class NativeResNet(nn.Module):
         return NativeSGD(self, lr=lr, momentum=momentum, weight_decay=weight_decay,
                          nesterov=nesterov, lars=lars, lars_eps=lars_eps, param_groups=param_groups)
 
-    def make_criterion(self) -> "NativeCrossEntropy":
-        return NativeCrossEntropy(self)
+    def make_criterion(self, label_smoothing: float = 0.0) -> "NativeCrossEntropy":
+        return NativeCrossEntropy(self, label_smoothing)
 
     def _apply(self, fn, recurse=True):  # .to()/.cuda()/.half() would break the flat views
         return self
@@ -1281,22 +1281,71 @@ class _XentFn(torch.autograd.Function):
         return torch.empty_like(logits), None, None
 
 
+class _XentSoftFn(torch.autograd.Function):
+    """:class:`_XentFn` against the soft target of two labels per row (K.xent_soft)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, labels_b, lam, eps, model: NativeResNet):
+        B = logits.shape[0]
+        loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        K.xent_soft(logits, labels, loss_rows, loss, labels_b=labels_b, lam=lam, eps=eps)
+        ctx.save_for_backward(logits, labels, *(() if labels_b is None else (labels_b,)))
+        ctx.model, ctx.lam, ctx.eps = model, lam, eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, *rest = ctx.saved_tensors
+        m: NativeResNet = ctx.model
+        B = logits.shape[0]
+        dlog16 = torch.empty(B, m.fc_rows, dtype=m.dtype, device=logits.device)
+        gdev = g.reshape(1).to(torch.float32).contiguous()
+        K.xent_soft(logits, labels, torch.empty(B, device=logits.device), None,
+                    labels_b=rest[0] if rest else None, lam=ctx.lam, eps=ctx.eps, dlog=dlog16,
+                    gscale=1.0 / B, gdev=gdev)
+        m._pending_dlog16 = dlog16
+        return torch.empty_like(logits), None, None, None, None, None
+
+
 class NativeCrossEntropy(nn.Module):
-    """CrossEntropyLoss (mean) fused with its gradient kernel for the native engine."""
+    """CrossEntropyLoss (mean) fused with its gradient kernel for the native engine.
+    ``label_smoothing`` (eps) and a second label per row with its weight (``labels_b``, ``lam``:
+    mixup / CutMix) select the soft-target kernel; with neither, the hard-label kernel runs."""
 
-    def __init__(self, model: Optional[NativeResNet] = None) -> None:
+    soft_targets = True      # forward takes (logits, labels, labels_b, lam): trainer.build_criterion
+
+    def __init__(self, model: Optional[NativeResNet] = None, label_smoothing: float = 0.0) -> None:
         super().__init__()
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
         self.model = model
+        self.label_smoothing = float(label_smoothing)
 
-    def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor,
+                labels_b: Optional[torch.Tensor] = None, lam: float = 1.0) -> torch.Tensor:
         m = self.model
+        eps = self.label_smoothing
         if m is None or not logits.is_cuda or logits.dtype != torch.float32:
-            return nn.functional.cross_entropy(logits.float(), labels)
+            x = logits.float()
+            if eps == 0.0 and labels_b is None:
+                return nn.functional.cross_entropy(x, labels)
+            from ..mix import soft_cross_entropy
+            return soft_cross_entropy(x, labels, labels_b, lam, eps)
+        if eps == 0.0 and labels_b is None:
+            if logits.requires_grad:
+                return _XentFn.apply(logits, labels, m)
+            B = logits.shape[0]
+            loss = torch.empty((), dtype=torch.float32, device=logits.device)
+            K.xent(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss)
+            return loss
+        lam = float(lam)
         if logits.requires_grad:
-            return _XentFn.apply(logits, labels, m)
+            return _XentSoftFn.apply(logits, labels, labels_b, lam, eps, m)
         B = logits.shape[0]
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        K.xent(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss)
+        K.xent_soft(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss,
+                    labels_b=labels_b, lam=lam, eps=eps)
         return loss
 
 

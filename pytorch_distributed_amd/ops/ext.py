@@ -110,6 +110,9 @@ _SIGS = {
     "pda_bn_bwd_finalize": [_V, _I, _I, _I, _I, _F, _V, _V, _V, _V, _V, _V, _V, _V, _F, _I, _V],
     "pda_bn_bwd_apply": [C.POINTER(BwdArgs), _V, _V, _V, _V, _V, _V, _I, _V],
     "pda_xent": [_V, _I, _I, _I, _V, _V, _V, _V, _I, _F, _V, _I, _I, _V],
+    "pda_xent_soft": [_V, _I, _I, _I, _V, _V, _F, _F, _V, _V, _V, _I, _F, _V, _I, _I, _V],
+    "pda_mean_rows": [_V, _I, _V, _V],
+    "pda_batch_mix": [_V, _V, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _I, _V],
     "pda_topk": [_V, _I, _I, _I, _V, _V, _V],
     "pda_col_sum": [_V, _I, _I, _I, _F, _V, _I, _I, _V],
     "pda_sgd_flat": [_V, _V, _V, _V, _L, _F, _F, _F, _V, _V, _I, _I, _V],

@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import struct
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
@@ -30,6 +31,7 @@ __all__ = [
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
     "aug_draw", "aug_resize_dev", "aug_record_bytes",
     "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg",
+    "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
 ]
 
 
@@ -1159,6 +1161,53 @@ def xent(logits: torch.Tensor, labels: torch.Tensor, loss_rows, loss, dlog=None,
     check(rc, "xent")
 
 
+def xent_soft_check(logits, labels, labels_b, lam: float, eps: float, dlog=None) -> Tuple[int, int]:
+    """Host-side validation of an :func:`xent_soft` call; returns (B, K). Pure Python, run before
+    the launch (NaN fails every comparison)."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("xent_soft: logits must be f32 [B, K] with unit column stride")
+    B, K = logits.shape
+    if B < 1 or K < 1 or logits.stride(0) < K:
+        raise ValueError(f"xent_soft: bad logits shape {tuple(logits.shape)} / row stride {logits.stride(0)}")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (B,) or not labels.is_contiguous():
+        raise ValueError(f"xent_soft: labels must be contiguous int64 [{B}], got {labels.dtype} "
+                         f"{tuple(labels.shape)}")
+    if labels_b is not None and (labels_b.dtype != labels.dtype or labels_b.shape != labels.shape
+                                 or not labels_b.is_contiguous() or labels_b.device != labels.device):
+        raise ValueError(f"xent_soft: labels_b must have the shape, dtype and device of labels "
+                         f"({labels.dtype} {tuple(labels.shape)}), got {labels_b.dtype} "
+                         f"{tuple(labels_b.shape)}")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"xent_soft: lam must lie in [0, 1], got {lam!r}")
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"xent_soft: eps (label smoothing) must lie in [0, 1), got {eps!r}")
+    if dlog is not None:
+        if dlog.dim() != 2 or dlog.shape[0] != B or dlog.shape[1] < K or not dlog.is_contiguous():
+            raise ValueError(f"xent_soft: dlog must be contiguous [{B}, >= {K}], got {tuple(dlog.shape)}")
+        if dlog.dtype not in ext.DT:
+            raise ValueError(f"xent_soft: unsupported dlog dtype {dlog.dtype}")
+    return B, K
+
+
+def xent_soft(logits: torch.Tensor, labels: torch.Tensor, loss_rows, loss, labels_b=None,
+              lam: float = 1.0, eps: float = 0.0, dlog=None, gscale: float = 1.0,
+              gdev: Optional[torch.Tensor] = None) -> None:
+    """:func:`xent` against the soft target q_k = eps/K + (1-eps) * (lam*[k==labels] +
+    (1-lam)*[k==labels_b]) (label smoothing eps, mixup / CutMix weight lam; ``labels_b`` None:
+    labels): loss_rows / loss = lse - sum_k q_k x_k, dlog = (softmax - q) * gscale * gdev[0]
+    (csrc/mix.hip). Arguments are validated on the host first (:func:`xent_soft_check`)."""
+    if loss_rows is None:
+        raise ValueError("xent_soft: loss_rows is required (the kernel writes it on every launch)")
+    lam, eps = float(lam), float(eps)
+    B, K = xent_soft_check(logits, labels, labels_b, lam, eps, dlog)
+    ld_out = dlog.shape[1] if dlog is not None else 0
+    dt = dt_of(dlog) if dlog is not None else 1
+    rc = ext.lib().pda_xent_soft(ptr(logits), B, K, logits.stride(0), ptr(labels), ptr(labels_b), lam,
+                                 eps, ptr(loss_rows), ptr(loss), ptr(dlog), ld_out, float(gscale),
+                                 ptr(gdev), dt, int(dlog is not None), stream(logits.device))
+    check(rc, "xent_soft")
+
+
 def topk_hits(logits, labels, hits) -> None:
     B, K = logits.shape
     rc = ext.lib().pda_topk(ptr(logits), B, K, logits.stride(0), ptr(labels), ptr(hits),
@@ -1472,6 +1521,82 @@ def aug_resize(packed, table_i64, table_f64, out, layout: int = AUG_S2D, fmt: in
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
     check(ext.lib().pda_aug_resize_fmt(ptr(packed), ptr(ti), ptr(tf), B, S, ptr(out), dt_of(out), layout,
                                        fmt, mean, std, stream(out.device)), "aug_resize")
+
+
+# ------------------------------------------------------------------ mixup / CutMix of a batch
+MIX_MIXUP, MIX_CUTMIX = 0, 1
+
+
+def mix_weights(lam: float) -> Tuple[float, float]:
+    """(lam, 1 - lam) as the float32 values :func:`batch_mix` hands its kernel: lam rounded to
+    float32, and one float32 subtraction from 1."""
+    f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]
+    lam32 = f32(float(lam))
+    return lam32, f32(1.0 - lam32)
+
+
+def batch_mix_check(x, out, layout: int, mode: int, lam: float, box=None) -> Tuple[int, int, tuple]:
+    """Host-side validation of a :func:`batch_mix` call; returns (B, S, box). Pure Python (the
+    kernel library is not loaded), run before the launch: the kernel trusts the shape and the box."""
+    if layout == AUG_S2D:
+        if x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] != 16:
+            raise ValueError(f"batch_mix: s2d input must be [B, S/2, S/2, 16], got {tuple(x.shape)}")
+        if x.dtype not in ext.DT:
+            raise ValueError(f"batch_mix: unsupported dtype {x.dtype}")
+        S = 2 * x.shape[1]
+    elif layout == AUG_NCHW:
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise ValueError(f"batch_mix: NCHW input must be [B, 3, S, S], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"batch_mix: the NCHW layout is f32, got {x.dtype}")
+        S = x.shape[2]
+    else:
+        raise ValueError(f"batch_mix: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
+    B = x.shape[0]
+    if B < 1 or S < 1 or S > (AUG_MAX_SIDE if layout == AUG_S2D else 26000):
+        raise ValueError(f"batch_mix: empty batch or image side {S} out of range")
+    if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError(f"batch_mix: out must have the shape, dtype and device of x "
+                         f"({tuple(x.shape)} {x.dtype} {x.device}), got {tuple(out.shape)} {out.dtype} "
+                         f"{out.device}")
+    if not x.is_contiguous() or not out.is_contiguous():
+        raise ValueError("batch_mix: x and out must be contiguous")
+    nbytes = x.numel() * x.element_size()
+    if x.device.type != "meta" and (x.data_ptr() < out.data_ptr() + nbytes
+                                    and out.data_ptr() < x.data_ptr() + nbytes):
+        raise ValueError("batch_mix: out overlaps x (sample b reads sample b-1: it runs out of place)")
+    if mode not in (MIX_MIXUP, MIX_CUTMIX):
+        raise ValueError(f"batch_mix: mode must be {MIX_MIXUP} (mixup) or {MIX_CUTMIX} (CutMix)")
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"batch_mix: lam must lie in [0, 1], got {lam!r}")
+    if mode == MIX_CUTMIX:
+        if box is None or len(box) != 4 or any(int(v) != v for v in box):
+            raise ValueError(f"batch_mix: CutMix needs an integer box (y1, y2, x1, x2), got {box!r}")
+        y1, y2, x1, x2 = (int(v) for v in box)
+        if not (0 <= y1 <= y2 <= S and 0 <= x1 <= x2 <= S):
+            raise ValueError(f"batch_mix: box rows [{y1}, {y2}) columns [{x1}, {x2}) outside the "
+                             f"{S}x{S} image")
+        box = (y1, y2, x1, x2)
+    else:
+        box = (0, 0, 0, 0)
+    return B, S, box
+
+
+def batch_mix(x, out, layout: int, mode: int, lam: float, box=None) -> None:
+    """Mix every sample of a finished batch with the one above it (sample 0 with the last;
+    torchvision's ``roll(1, 0)``) into ``out`` (one launch, csrc/mix.hip). ``layout``: ``AUG_S2D``
+    [B, S/2, S/2, 16] (f32 / bf16 / f16) or ``AUG_NCHW`` [B, 3, S, S] f32. ``MIX_MIXUP``: out =
+    lam*x + (1-lam)*partner, in f32 with one rounding; ``MIX_CUTMIX``: pixels with y1 <= y < y2 and
+    x1 <= x < x2 (``box`` = (y1, y2, x1, x2)) take the partner's bits, every other x's."""
+    lam = float(lam)
+    B, S, box = batch_mix_check(x, out, layout, mode, lam, box)
+    if x.device.type != "cuda":
+        raise ValueError("batch_mix runs on a GPU; the batch is on " + str(x.device))
+    if x.data_ptr() % 16 or out.data_ptr() % 16:
+        raise ValueError("batch_mix: x and out must be 16-byte aligned")
+    lam32, oml32 = mix_weights(lam)
+    check(ext.lib().pda_batch_mix(ptr(x), ptr(out), B, S, dt_of(x), layout, mode, lam32, oml32, *box,
+                                  0, stream(x.device)), "batch_mix")
 
 
 AUG_TRAIN, AUG_VAL = 0, 1

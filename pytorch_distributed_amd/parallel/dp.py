@@ -185,10 +185,14 @@ class DataParallel(nn.Module):
         kw.pop("lars", None), kw.pop("lars_eps", None)
         return torch.optim.SGD(params, **kw)
 
-    def make_criterion(self):
+    def make_criterion(self, label_smoothing: float = 0.0):
         if not self.replicas and hasattr(self.module, "make_criterion"):
-            return self.module.make_criterion()
-        return nn.CrossEntropyLoss()   # gathered logits: gradient flows back through _Gather
+            return self.module.make_criterion(label_smoothing)
+        # gathered logits: gradient flows back through _Gather
+        if label_smoothing > 0:
+            from ..mix import SoftCrossEntropy
+            return SoftCrossEntropy(label_smoothing)
+        return nn.CrossEntropyLoss()
 
     def input_generator(self, ds):
         return self.module.input_generator(ds) if hasattr(self.module, "input_generator") else None

@@ -132,6 +132,18 @@ def _graphed_step(model, optimizer, ctx: Context):
     return g
 
 
+def _batch_mixer(ctx: Context):
+    """``MX_MIXUP`` / ``MX_CUTMIX``: the run's :class:`~pytorch_distributed_amd.mix.BatchMixer`
+    (kept on the context: one output buffer serves every epoch), else None."""
+    if not (ctx.cfg.mixup > 0 or ctx.cfg.cutmix > 0):
+        return None
+    mixer = ctx.extra.get("mixer")
+    if mixer is None:
+        from .mix import BatchMixer
+        mixer = ctx.extra["mixer"] = BatchMixer(ctx.cfg, ctx)
+    return mixer
+
+
 def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: Context,
           start_step: int, best_acc: float, save_path: Path) -> int:
     """One epoch of training (reference ``restnet_ddp.py:19-47``). Returns steps run."""
@@ -139,10 +151,14 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     cfg = ctx.cfg
     steps = 0
     scaler = ctx.scaler
+    soft = cfg.soft_targets
+    mixer = _batch_mixer(ctx)
     from .utils.metrics import StepProfiler
     prof = StepProfiler(int(os.environ.get("MX_PROFILE", "0") or 0) if epoch == 0 else 0, save_path,
                         ctx.rank)
-    graphed = _graphed_step(model, optimizer, ctx)
+    # soft targets run the eager branches: a captured step (MX_GRAPH=1, DataParallel's train_step)
+    # takes hard labels only
+    graphed = None if soft else _graphed_step(model, optimizer, ctx)
     sb = ctx.extra.get("step_busy")     # device-busy fallback (utils/gpu_util.py StepBusy)
     for step, (samples, labels) in dataloader.iter_from(start_step):
         if ctx.cfg.script == "single" and cfg.log_every and step % cfg.log_every == 0:
@@ -151,15 +167,22 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             sb.begin()
         samples = samples.to(ctx.device, non_blocking=True)
         labels = labels.to(ctx.device, non_blocking=True)
+        soft_args = ()                   # (labels_b, lam): the criterion's two further arguments
+        if soft:
+            labels_b, lam = None, 1.0
+            if mixer is not None:
+                samples, labels, labels_b, lam = mixer(samples, labels, epoch, step)
+            soft_args = (labels_b, lam)
         if graphed is not None and graphed.accepts(samples):
             graphed.run_batch(samples, labels)      # MX_GRAPH=1: the whole step, one graph launch
             loss = graphed.loss
-        elif getattr(model, "graph_step_ok", None) is not None and model.graph_step_ok(scaler):
+        elif (not soft and getattr(model, "graph_step_ok", None) is not None
+              and model.graph_step_ok(scaler)):
             loss = model.train_step(samples, labels, optimizer)     # DP: HIP-graph replay per GPU
         elif scaler is not None and scaler.enabled:
             with _autocast(ctx):
                 outputs = model(samples)
-                loss = criterion(outputs, labels)
+                loss = criterion(outputs, labels, *soft_args)
             scaler.scale(loss).backward()
             scaler.step(optimizer)
             scaler.update()
@@ -168,7 +191,8 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             with _autocast(ctx):
                 outputs = model(samples)
             optimizer.zero_grad()
-            loss = criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels)
+            loss = criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels,
+                             *soft_args)
             loss.backward()
             optimizer.step()
         if sb is not None:
@@ -353,10 +377,40 @@ def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
     return torch.optim.SGD(groups, **kw)
 
 
+def _refuse_soft_targets(cfg: RunConfig, model: nn.Module, ctx: Context) -> None:
+    """Captured steps bake the loss arguments in at capture: ``MX_GRAPH=1`` and DataParallel over
+    several devices refuse label smoothing / mixup / CutMix (ValueError, before training starts)."""
+    if not cfg.soft_targets:
+        return
+    from .mix import MIX_REFUSAL
+    if cfg.graph and ctx.engine == "native":
+        raise ValueError(MIX_REFUSAL.format(what="MX_GRAPH=1"))
+    if getattr(model, "replicas", None) or (getattr(model, "force_replay", False)
+                                            and getattr(model, "_native", False)):
+        raise ValueError(MIX_REFUSAL.format(
+            what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+
+
 def build_criterion(ctx: Context, model: nn.Module):
+    """The loss: the native engine's fused kernel, else ``nn.CrossEntropyLoss``. With
+    ``MX_LABEL_SMOOTHING`` / ``MX_MIXUP`` / ``MX_CUTMIX`` the criterion takes ``(outputs, labels,
+    labels_b, lam)``: the native one with the smoothing passed through, on the torch engine and
+    the CPU :class:`~pytorch_distributed_amd.mix.SoftCrossEntropy`."""
+    cfg = ctx.cfg
+    _refuse_soft_targets(cfg, model, ctx)
     inner = _factory_owner(model, "make_criterion")
     if hasattr(inner, "make_criterion"):
-        return inner.make_criterion()
+        if cfg.label_smoothing > 0:
+            crit = inner.make_criterion(label_smoothing=cfg.label_smoothing)
+        else:
+            crit = inner.make_criterion()
+        # a factory that wraps a torch module (DataParallel on the torch engine or the CPU) hands
+        # back a hard-label loss: soft targets need one that takes (labels_b, lam)
+        if not cfg.soft_targets or getattr(crit, "soft_targets", False):
+            return crit
+    if cfg.soft_targets:
+        from .mix import SoftCrossEntropy
+        return SoftCrossEntropy(cfg.label_smoothing)
     return nn.CrossEntropyLoss()
 
 
