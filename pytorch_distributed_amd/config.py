@@ -56,6 +56,9 @@ class RunConfig:
     label_smoothing: float = 0.0     # cross-entropy label smoothing eps in [0, 1)
     mixup: float = 0.0               # mixup Beta(alpha, alpha) (0 = off)
     cutmix: float = 0.0              # CutMix Beta(alpha, alpha) (0 = off)
+    ema: float = 0.0                 # weight-EMA decay in (0, 1) (0 = off)
+    ema_every: int = 1               # EMA update interval in optimizer steps
+    ema_warmup: bool = True          # EMA decay min(decay, (1 + t) / (10 + t)) over its updates t
 
     @property
     def soft_targets(self) -> bool:
@@ -110,6 +113,9 @@ _ENV = {
     "MX_LABEL_SMOOTHING": ("label_smoothing", float),
     "MX_MIXUP": ("mixup", float),
     "MX_CUTMIX": ("cutmix", float),
+    "MX_EMA": ("ema", float),
+    "MX_EMA_EVERY": ("ema_every", int),
+    "MX_EMA_WARMUP": ("ema_warmup", _bool),
 }
 
 
@@ -160,6 +166,10 @@ def config_for(script: str, env: Optional[dict] = None,
     for var, v in (("MX_MIXUP", cfg.mixup), ("MX_CUTMIX", cfg.cutmix)):
         if not v >= 0 or v == float("inf"):
             raise ValueError(f"{var} is a Beta(alpha, alpha) parameter >= 0 (0 = off), got {v!r}")
+    if not 0 <= cfg.ema < 1:
+        raise ValueError(f"MX_EMA is a decay in (0, 1) (0 = off), got {cfg.ema!r}")
+    if cfg.ema_every < 1:
+        raise ValueError(f"MX_EMA_EVERY is an interval of >= 1 optimizer steps, got {cfg.ema_every!r}")
     if cfg.nesterov and not cfg.momentum > 0:
         raise ValueError("MX_NESTEROV needs momentum > 0")
     if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:

@@ -142,6 +142,9 @@ _SIGS = {
     "pda_seg_chunk": [],
     "pda_seg_norms": [_V, _V, _L, _V, _V, _V, _V, _I, _I, _V, _V],
     "pda_sgd_seg": [_V, _V, _V, _V, _L, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _V],
+    "pda_ema_check": [_V, _I, _I, _F, _I],
+    "pda_ema_chunk": [],
+    "pda_ema": [_V, _I, _I, _F, _I, _V],
 }
 
 

@@ -1398,6 +1398,81 @@ def sgd_seg(p, g, buf, shadow, tables: SegTables, initialized: bool, inv_scale=N
     _seg_check(rc, "sgd_seg")
 
 
+# ------------------------------------------------------------------ weight EMA (csrc/ema.hip)
+EMA_CHUNK = 4096                          # elements one block of the EMA kernel handles
+EMA_LERP, EMA_COPY, EMA_SWAP = 0, 1, 2    # csrc/ema.hip EmaMode
+
+
+class EmaRange(C.Structure):
+    """One (e, p[, 16-bit shadow of p]) range of ``count`` 4-byte elements (csrc/ema.hip)."""
+    _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("shadow", C.c_void_p), ("count", C.c_longlong)]
+
+
+_EMA_ERRORS = {-1: "bad mode or shadow dtype, or a missing e / p buffer",
+               -2: "a range does not start 16-byte aligned (8-byte for the shadow)",
+               -3: "a negative element count", -4: "e, p and shadow ranges overlap",
+               -5: "w is not finite or lies outside [0, 1]"}
+
+
+class EmaRanges:
+    """A checked range table of :func:`ema_update`: ``ranges`` is a sequence of ``(e, p)`` or
+    ``(e, p, shadow)`` tensors -- e and p contiguous f32 of one length on one GPU, the optional
+    shadow bf16 or fp16 of that length. Built once, launched many times: the rows hold the tensors'
+    addresses (and the tensors themselves, so they stay alive)."""
+
+    def __init__(self, ranges) -> None:
+        self.tensors = [tuple(r) + (None,) * (3 - len(r)) for r in ranges]
+        self.rows = (EmaRange * len(self.tensors))()
+        self.device, self.shadow_dtype = None, None
+        for row, (e, p, sh) in zip(self.rows, self.tensors):
+            for name, t in (("e", e), ("p", p)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                    raise ValueError(f"ema_update: {name} is an f32 tensor, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)}")
+            if sh is not None:
+                if sh.dtype not in (torch.bfloat16, torch.float16):
+                    raise ValueError("ema_update: the shadow is bf16 or fp16")
+                if self.shadow_dtype not in (None, sh.dtype):
+                    raise ValueError("ema_update: every shadow of one launch has the same dtype")
+                self.shadow_dtype = sh.dtype
+            if self.device is None:
+                self.device = e.device
+            for name, t in (("e", e), ("p", p), ("shadow", sh)):
+                if t is None:
+                    continue
+                if t.device != self.device or not t.is_contiguous() or t.numel() != e.numel():
+                    raise ValueError(f"ema_update: {name} must be a contiguous tensor of {e.numel()} "
+                                     f"elements on {self.device}")
+            row.e, row.p, row.shadow, row.count = ptr(e), ptr(p), ptr(sh), e.numel()
+        if self.device is not None and self.device.type != "cuda":
+            raise ValueError(f"ema_update runs on a GPU; the buffers are on {self.device}")
+
+
+def ema_weight(w: float) -> float:
+    """The float32 value of ``w`` the kernel computes with (NaN and out-of-range values pass through
+    for the launcher to refuse)."""
+    return C.c_float(float(w)).value
+
+
+def ema_update(ranges, mode: int, w: float = 0.0) -> None:
+    """One launch over ``ranges`` (an :class:`EmaRanges`, or the sequence it is built from):
+    ``EMA_LERP`` e = fmaf(w, p - e, e) with the float32 ``w``; ``EMA_COPY`` e = p bit for bit;
+    ``EMA_SWAP`` e and p exchange their bits and each given shadow receives the 16-bit cast of the
+    new p. Elements outside the ranges stay; bad ranges raise ValueError and launch nothing."""
+    if not isinstance(ranges, EmaRanges):
+        ranges = EmaRanges(ranges)
+    if mode not in (EMA_LERP, EMA_COPY, EMA_SWAP):
+        raise ValueError(f"ema_update: mode is EMA_LERP, EMA_COPY or EMA_SWAP, got {mode!r}")
+    if len(ranges.rows) == 0:
+        return
+    dt = dt_of(ranges.shadow_dtype) if ranges.shadow_dtype is not None else 1
+    rc = ext.lib().pda_ema(C.cast(ranges.rows, C.c_void_p), len(ranges.rows), int(mode), float(w), dt,
+                           stream(ranges.device))
+    if rc < 0:
+        raise ValueError(f"ema_update: {_EMA_ERRORS.get(rc, f'bad ranges ({rc})')}")
+    check(rc, "ema_update")
+
+
 def pack_stem(src_ohwi, dst, Cout=64, RS=49, Cin=3, Cpad=8) -> None:
     Kpad = dst.shape[1]
     check(ext.lib().pda_pack_stem(ptr(src_ohwi), ptr(dst), Cout, RS, Cin, Cpad, Kpad, dt_of(dst),

@@ -18,6 +18,7 @@ re-reading skipped batches).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 from dataclasses import dataclass, field
@@ -159,6 +160,7 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     # soft targets run the eager branches: a captured step (MX_GRAPH=1, DataParallel's train_step)
     # takes hard labels only
     graphed = None if soft else _graphed_step(model, optimizer, ctx)
+    ema = ctx.extra.get("ema")          # MX_EMA: the weight average follows every optimizer step
     sb = ctx.extra.get("step_busy")     # device-busy fallback (utils/gpu_util.py StepBusy)
     for step, (samples, labels) in dataloader.iter_from(start_step):
         if ctx.cfg.script == "single" and cfg.log_every and step % cfg.log_every == 0:
@@ -195,6 +197,8 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
                              *soft_args)
             loss.backward()
             optimizer.step()
+        if ema is not None:
+            ema.update()
         if sb is not None:
             sb.end()
         _sync_step(ctx)
@@ -206,7 +210,8 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
                 if ctx.is_main:
                     save_latest(save_path, _unwrap(model).state_dict(), optimizer.state_dict(),
                                 scheduler.state_dict(), best_acc, epoch, step + 1,
-                                scaler.state_dict() if scaler is not None and scaler.enabled else None)
+                                scaler.state_dict() if scaler is not None and scaler.enabled else None,
+                                **({"ema_sd": ema.state_dict()} if ema is not None else {}))
                     print(f"suspend: saved {save_path / 'latest.pt'} at epoch {epoch} step {step + 1}",
                           flush=True)
                 go_suspend()
@@ -214,8 +219,9 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     return steps
 
 
-def validate(dataloader, model, criterion, epoch: int, ctx: Context) -> float:
-    """Top-1/top-5 validation (reference ``restnet_ddp.py:50-72``).
+def validate(dataloader, model, criterion, epoch: int, ctx: Context, prefix: str = "") -> float:
+    """Top-1/top-5 validation (reference ``restnet_ddp.py:50-72``); ``prefix`` goes in front of the
+    log line (``"EMA "``: the pass over the averaged weights).
 
     Counters live on the device (fixes Q3); in DDP they are all-reduced in ONE
     4-element collective (instead of 4 ``dist.reduce`` calls) so every rank returns
@@ -252,7 +258,7 @@ def validate(dataloader, model, criterion, epoch: int, ctx: Context) -> float:
     loss_val = loss / ctx.world / nb
     total = max(total, 1.0)
     if ctx.is_main:
-        print(f'Epoch: {epoch}, Loss: {loss_val}, Acc1: {100 * c1 / total:.2f}%, '
+        print(f'{prefix}Epoch: {epoch}, Loss: {loss_val}, Acc1: {100 * c1 / total:.2f}%, '
               f'Acc5: {100 * c5 / total:.2f}%', flush=True)
     return c1 / total
 
@@ -467,6 +473,14 @@ def run(cfg: RunConfig, mode: str, local_rank: int = 0, nprocs: Optional[int] = 
         best_acc, start_epoch, start_step = ckpt["acc"], ckpt["epoch"], ckpt["step"]
         if ctx.is_main:
             print(f"resume: epoch {start_epoch} step {start_step} (best acc {best_acc})", flush=True)
+    if cfg.ema > 0:
+        # after the resume: the average starts from the weights the run continues with, unless the
+        # checkpoint brings its own (every DDP rank averages its own, identical weights)
+        from .ema import build_ema
+        ema = ctx.extra["ema"] = build_ema(cfg, model, ctx)
+        if ckpt is not None and "ema" in ckpt:
+            ema.load_state_dict(ckpt["ema"])
+    ema = ctx.extra.get("ema")
 
     for epoch in range(start_epoch, cfg.epochs):
         t1 = time.time()
@@ -491,19 +505,26 @@ def run(cfg: RunConfig, mode: str, local_rank: int = 0, nprocs: Optional[int] = 
         start_step = 0
         scheduler.step()
         acc = validate(val_loader, model, criterion, epoch, ctx)
-        t2 = time.time()
-        if cfg.empty_cache == "epoch" and device.type == "cuda":
-            torch.cuda.empty_cache()
-        if ctx.is_main:
-            print("cost time per epoch: {:.4f} s".format(t2 - t1), flush=True)
-            ctx.metrics.write(epoch=epoch, steps=steps, epoch_s=t2 - t1, acc1=acc,
-                              images=steps * per_rank_batch * ctx.world, gpu_mem_gb=gpu_mem_gb(),
-                              gpu_util_pct=util, gpu_util_method=util_method if util is not None else None,
-                              engine=engine, dtype=str(dtype))
-            if acc > best_acc:
-                best_acc = acc
-                print(f'New Best Acc: {100 * acc:.2f}%!', flush=True)
-                save_best(save_path, _unwrap(model).state_dict())
+        # MX_EMA: a second pass over the averaged weights, which then decide (and are) best.pt
+        with ema.swapped() if ema is not None else contextlib.nullcontext():
+            more = {}
+            if ema is not None:
+                more["ema_acc1"] = validate(val_loader, model, criterion, epoch, ctx, prefix="EMA ")
+            t2 = time.time()
+            if cfg.empty_cache == "epoch" and device.type == "cuda":
+                torch.cuda.empty_cache()
+            if ctx.is_main:
+                print("cost time per epoch: {:.4f} s".format(t2 - t1), flush=True)
+                ctx.metrics.write(epoch=epoch, steps=steps, epoch_s=t2 - t1, acc1=acc,
+                                  images=steps * per_rank_batch * ctx.world, gpu_mem_gb=gpu_mem_gb(),
+                                  gpu_util_pct=util,
+                                  gpu_util_method=util_method if util is not None else None,
+                                  engine=engine, dtype=str(dtype), **more)
+                acc = more.get("ema_acc1", acc)
+                if acc > best_acc:
+                    best_acc = acc
+                    print(f'New Best Acc: {100 * acc:.2f}%!', flush=True)
+                    save_best(save_path, _unwrap(model).state_dict())
     if distributed:
         import torch.distributed as dist
         from .launch import host_group

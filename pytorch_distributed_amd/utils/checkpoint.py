@@ -2,7 +2,8 @@
 
 * ``latest.pt`` = ``{'model','optimizer','scheduler','acc','epoch','step'}``
   written on suspend (reference ``restnet_ddp.py:37-44``), plus the optional
-  superset key ``'scaler'`` for AMP (quirk Q9: the reference never saved it).
+  superset key ``'scaler'`` for AMP (quirk Q9: the reference never saved it) and ``'ema'`` for
+  a run with ``MX_EMA`` (the weight average's state, ``ema.py``).
 * ``best.pt`` = bare model ``state_dict`` (reference ``restnet_ddp.py:150``).
 
 Model state is always torchvision layout (OIHW conv weights, torchvision key
@@ -53,7 +54,7 @@ def save_atomic(obj: Any, path) -> None:
 
 
 def save_latest(save_path, model_sd, optimizer_sd, scheduler_sd, acc, epoch, step,
-                scaler_sd: Optional[dict] = None) -> Path:
+                scaler_sd: Optional[dict] = None, ema_sd: Optional[dict] = None) -> Path:
     state: Dict[str, Any] = {
         "model": model_sd,
         "optimizer": optimizer_sd,
@@ -64,6 +65,8 @@ def save_latest(save_path, model_sd, optimizer_sd, scheduler_sd, acc, epoch, ste
     }
     if scaler_sd is not None:
         state["scaler"] = scaler_sd
+    if ema_sd is not None:
+        state["ema"] = ema_sd
     p = Path(save_path) / LATEST
     save_atomic(state, p)
     return p
