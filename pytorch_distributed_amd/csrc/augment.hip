@@ -31,6 +31,7 @@
 //   R = Y + 1.402 cr, G = Y - 0.344136 cb - 0.714136 cr, B = Y + 1.772 cb, clamped to [0, 255],
 // then normalised as above. A grey image has filtered chroma of exactly 0 and R = G = B = Y.
 #include "common.h"
+#include "pda_api.h"
 
 namespace {
 
@@ -372,12 +373,6 @@ __global__ __launch_bounds__(AUG_NT) void aug_draw_kernel(const long long* __res
 
 extern "C" {
 
-// packed: device bytes; ti: device int64 [B][4] = byte offset, H, W, flip; tf: device f64 [B][4] =
-// x0, y0, x1, y1; mean / std: HOST float[3]. layout 0: s2d [B][S/2][S/2][16] of dtype dt (16-B
-// aligned), 1: NCHW f32. fmt 0: records are HWC RGB (3*H*W bytes); 1: YCbCr 4:2:0 (Y plane, then
-// the interleaved half-resolution CbCr plane: H*W + 2*((H+1)/2)*((W+1)/2) bytes). The tables must
-// have been validated by the caller (ops/native_ops.py aug_check): the kernel trusts offsets, sizes
-// and boxes.
 int pda_aug_resize_fmt(const void* packed, const long long* ti, const double* tf, int B, int S,
                        void* out, int dt, int layout, int fmt, const float* mean, const float* std,
                        hipStream_t st) {
@@ -411,17 +406,6 @@ int pda_aug_resize_fmt(const void* packed, const long long* ti, const double* tf
   return (int)hipGetLastError();
 }
 
-// RGB records: the folder path and version-1 packed files
-int pda_aug_resize(const void* packed, const long long* ti, const double* tf, int B, int S, void* out,
-                   int dt, int layout, const float* mean, const float* std, hipStream_t st) {
-  return pda_aug_resize_fmt(packed, ti, tf, B, S, out, dt, layout, 0, mean, std, st);
-}
-
-// ids: device int64 [B], every one in [0, N); index: device int64 [N][4] = byte offset, H, W, label,
-// validated on the host when the file was opened (data/packed.py); batch_off: device int64 [B] byte
-// offsets that replace the index's (host residency), or null. mode 0: train draw with scale bounds
-// s0 <= s1 and ratio bounds r0 <= r1; 1: val box of Resize(resize) -> CenterCrop(S), resize >= S.
-// Writes ti [B][4], tf [B][4] (pda_aug_resize's tables) and labels [B].
 int pda_aug_draw(const long long* ids, const long long* index, const long long* batch_off, int B,
                  long long N, unsigned seed, int split_id, unsigned epoch, int mode, int S, int resize,
                  double s0, double s1, double r0, double r1, long long* ti, double* tf,

@@ -16,6 +16,7 @@
 //   bn_bwd_apply    : dy = k1*dz + k2*y + k3 (dz recomputed, or read back from the tail buffer)
 //   maxpool_bwd     : deterministic gather of max-pool gradients through the argmax bytes
 #include "common.h"
+#include "pda_api.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -107,23 +108,7 @@ __global__ __launch_bounds__(256) void bn_finalize_tot_kernel(
 // an f64 slab -- 16-B loads, (channel quad x slab lane) threads, fixed-order lane combine -- and
 // publishes it write-through (sc1 stores, vmcnt(0), barrier, agent-scope arrival counter); the
 // group's last arriving block (agent acquire) sums the S slabs in slab order and finalizes.
-struct BnFwdOut {  // mirrors ops/ext.py BnFwdOut
-  const float* gamma; const float* beta;
-  float eps, momentum;
-  float* mean; float* invstd; float* scale; float* shift;
-  float* rmean; float* rvar; long long* nbt;
-  int update;
-  double* tot;   // non-null: f64 totals [2][C] instead of the finalize (bn_finalize_tot after)
-};
-
-struct BnBwdOut {  // mirrors ops/ext.py BnBwdOut; branch b = 0: BN of y, 1: shortcut BN of y2
-  float count, gscale;
-  int accumulate;
-  const float* gamma[2]; const float* mean[2]; const float* invstd[2];
-  float* dgamma[2]; float* dbeta[2];
-  float* k;      // [NQ-1][3][C]: dy_b = k0*dz + k1*y_b + k2
-};
-
+// The outputs of either kind are a BnFwdOut / BnBwdOut (pda_api.h).
 __device__ __forceinline__ void st_wt(double* q, double v) {   // write-through (sc1) store
   __hip_atomic_store(q, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1161,9 +1146,6 @@ inline int stream_grid(long long n8, int C) {
 
 extern "C" {
 
-// Streaming apply kernels (see StreamCfg): unroll < 0 = auto with -unroll chunks (-1: 4) for
-// tensors >= min_mb MiB, 0 = the one-chunk kernels, 1/2/4 = that many chunks for every shape;
-// ntm / cap apply to the multi-chunk launches. Returns the previous unroll.
 int pda_set_stream_cfg(int unroll, int ntm, int cap, int min_mb) {
   const int prev = g_stream.unroll;
   const int a = unroll < 0 ? -unroll : unroll;
@@ -1192,10 +1174,7 @@ int pda_bn_finalize_tot(const double* tot, int C, double count, const float* gam
   return (int)hipGetLastError();
 }
 
-// Partial statistics -> BatchNorm coefficients in one launch (bn_stats_kernel). slabs: f64 >=
-// S * nq * C; cnt: int32 >= ceil(C / 256), zero (and left zero). Returns -2 on a bad shape.
-// cg: channels per block group (a power of two in [4, 256]; 0 = 256). Fewer channels per group
-// give each channel quad more lanes (SL = 1024 / cg): shorter serial chains in both levels.
+// channels per block group of pda_bn_fwd_stats / pda_bn_bwd_stats (cg as given; 0 or bad = 256)
 static int stats_cg(int C, int cg) {
   if (cg <= 0 || cg > 256 || (cg & (cg - 1)) || cg < 4) cg = 256;
   return C < cg ? C : cg;
@@ -1242,8 +1221,6 @@ static FastDiv make_div(uint32_t d) {
   return f;
 }
 
-// mask (nullable): one byte per 8 elements, bit e = (output element e > 0) -- lets the backward of an
-// identity-shortcut tail skip re-reading the residual to rebuild its ReLU mask
 int pda_bn_apply(const void* y, const float* sc, const float* sh, const void* r2, const float* sc2,
                  const float* sh2, void* out, long long numel, int C, int mode, int relu,
                  void* mask, int dt, hipStream_t st) {
@@ -1306,14 +1283,6 @@ int pda_tail_pool(const void* y, const float* sc, const float* sh, const void* r
   return (int)hipGetLastError();
 }
 
-struct BwdArgsC {  // mirrors ops/ext.py
-  const void* g1; const void* g2; const void* gp; int HW;
-  const void* y; const float* sc; const float* sh;
-  const void* y2; const float* sc2; const float* sh2;
-  int mode; void* dz_out;
-  float* part; int nq; long long rows; int C;
-};
-
 static BwdArgs to_args(const BwdArgsC* c) {
   BwdArgs a;
   a.g1 = (const void*)c->g1; a.g2 = (const void*)c->g2; a.gp = (const void*)c->gp; a.HW = c->HW;
@@ -1324,7 +1293,6 @@ static BwdArgs to_args(const BwdArgsC* c) {
   return a;
 }
 
-// G = number of partial slabs written (returned through *G_out); part must hold G*nq*C floats.
 int pda_bn_bwd_reduce(const BwdArgsC* c, int G, int dt, hipStream_t st) {
   BwdArgs a = to_args(c);
   a.rows_per_block = (a.rows + G - 1) / G;
@@ -1334,7 +1302,6 @@ int pda_bn_bwd_reduce(const BwdArgsC* c, int G, int dt, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-// stem backward reduce (maxpool gather + ReLU mask + dz store + partials [G][2][C])
 int pda_stem_bwd_reduce(const void* dout, const void* dout2, const void* arg, const void* y,
                         const float* sc, const float* sh, void* dz_out, float* part, int G, int N,
                         int H, int W, int C, int Ho, int Wo, int dt, hipStream_t st) {
@@ -1361,7 +1328,6 @@ int pda_bn_bwd_finalize(const float* part, int G, int nq, int qy, int C, float c
   return (int)hipGetLastError();
 }
 
-// Both branches of a downsample tail in one pass (16-bit; -1 for other dtypes): k = [2][3][C].
 int pda_bn_bwd_apply2(const void* dz, const void* y, const void* y2, const float* k, void* dy,
                       void* dy2, long long rows, int C, int dt, hipStream_t st) {
   if ((dt != DT_BF16 && dt != DT_F16) || (C & 7) || rows * (C / 8) >= (1ll << 31)) return -1;

@@ -23,6 +23,7 @@
 // Forward epilogue stages the tile through LDS for 16-B coalesced stores and emits per-channel
 // partial sum / sum-of-squares (BatchNorm statistics) per M-tile -- no extra pass over Y.
 #include "common.h"
+#include "pda_api.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -1860,10 +1861,6 @@ static FastDiv make_div(uint32_t d) {
   return f;
 }
 
-struct ConvDesc {  // mirrors pytorch_distributed_amd/ops/ext.py ConvDesc
-  int Nb, H, W, Cin, Cout, R, S, stride, pad, Ho, Wo;
-};
-
 template <int PASS, int DT, int BM, int BN, int ST>
 static int launch(const ConvParams& p, dim3 grid, hipStream_t st) {
   if constexpr ((PASS == WGRAD_BNA || PASS == DGRAD_BNF || PASS == WGRAD_GRAM || PASS == FWD_TAIL) &&
@@ -1966,8 +1963,6 @@ static void fill_geom(ConvParams& p, const ConvDesc& d) {
 
 extern "C" {
 
-// Y[M=Nb*Ho*Wo][Cout] = conv(X, W). W: [Cout][Kpad] 16-bit. stats: [ceil(M/bm)][3][Cout] shifted
-// partials or null.
 int pda_conv_fwd(const ConvDesc* d, const void* x, const void* w, int Kpad, void* y, int out_f32,
                  int out_pitch, const float* bias, float* stats, int relu, const float* pro_sc,
                  const float* pro_sh, int dt, int bm, int bn, hipStream_t st) {
@@ -1986,10 +1981,6 @@ int pda_conv_fwd(const ConvDesc* d, const void* x, const void* w, int Kpad, void
   return dispatch<FWD>(dt, bm, bn, p, dim3(tiles, 1), st);
 }
 
-// FWD_TAIL (see the Pass enum): Y = conv(a, W) of a 1x1 stride-1 conv whose input
-// a = relu(y3 * sc + sh + r) (mode 1, r = res) or relu(y3 * sc + sh + res * sc2 + sh2) (mode 2) is
-// formed while staging; a is written to a_out (and its ReLU bitmask to mask, mode 1, nullable) by
-// the first N-tile's blocks. Register-staged single-stage tiles (-128, 64) / (-128, 128).
 int pda_conv_fwd_tail(const ConvDesc* d, const void* y3, const void* w, int Kpad, void* y,
                       float* stats, const float* sc, const float* sh, const void* res,
                       const float* sc2, const float* sh2, void* a_out, void* mask, int mode, int dt,
@@ -2019,15 +2010,6 @@ int pda_conv_fwd_tail(const ConvDesc* d, const void* y3, const void* w, int Kpad
 #undef TAIL_CASE
   return -1;
 }
-
-// dX[Nb,H,W,Cin] = conv_transpose(dY, W). Every dX element is written (zeros where no tap lands).
-struct BnEpi {  // mirrors ops/ext.py BnEpi
-  int mode, nq;
-  const void* y; const float* sc; const float* sh;
-  const void* y2; const float* sc2; const float* sh2;
-  const void* g2; float* part;
-  const void* mask;
-};
 
 static int dgrad_params(ConvParams& p, const ConvDesc* d, const void* dy, const void* w, void* dx,
                         const BnEpi* epi) {
@@ -2083,10 +2065,6 @@ int pda_conv_dgrad(const ConvDesc* d, const void* dy, const void* w, void* dx, c
   return dispatch<DGRAD>(dt, bm, bn, p, dim3(tiles, d->stride * d->stride), st);
 }
 
-// DGRAD of a 1x1 conv whose dY = k1*dz + k2*y + k3 is folded (see DGRAD_BNF): dz [Nb,Ho,Wo,Cout];
-// wf = [k1 o W ; G] ([Cout + Cin][Cin], pda_bn_fold); xa [Nb,H,W,Cin] the Gram operand (the conv's
-// forward input; xa_sc / xa_sh: its BN+ReLU prologue, or null); dbias [Cin] f32. Register-staged
-// tiles (-128, 64), (-128, 128), (64, 64), (64, 128); -1 otherwise.
 int pda_conv_dgrad_bnf(const ConvDesc* d, const void* dz, const void* wf, void* dx, const BnEpi* epi,
                        const void* xa, const float* xa_sc, const float* xa_sh, const float* dbias,
                        int dt, int bm, int bn, hipStream_t st) {
@@ -2115,8 +2093,6 @@ int pda_conv_dgrad_bnf(const ConvDesc* d, const void* dz, const void* wf, void* 
   return -1;
 }
 
-// Wf = [k1 o W ; W^T diag(k2) W] and b = W^T k3 of a 1x1 conv (W [Cout][Cin] 16-bit, k = [k1;k2;k3]
-// 3 x Cout f32): the operands of pda_conv_dgrad_bnf. Cout, Cin multiples of 64.
 int pda_bn_fold(const void* w, const float* k, int Cout, int Cin, void* wf, float* bias, int dt,
                 hipStream_t st) {
   if ((Cout % 64) || (Cin % 64) || Cin > 4096) return -2;
@@ -2133,8 +2109,6 @@ int pda_bn_fold(const void* w, const float* k, int Cout, int Cin, void* wf, floa
   return (int)hipGetLastError();
 }
 
-// As pda_conv_wgrad with dY formed while staging from the BatchNorm backward: dY = k1*dz + k2*y + k3
-// (per output channel; the stem: Cout 64). 16-bit, 64x128 tiles only (wider ones spill); -1 otherwise.
 int pda_conv_wgrad_bna(const ConvDesc* d, const void* dz, const void* y, const float* k1,
                        const float* k2, const float* k3, const void* x, float* slab, int splits,
                        int k_chunk, const float* pro_sc, const float* pro_sh, int dt, int bm, int bn,
@@ -2166,9 +2140,6 @@ int pda_conv_wgrad_bna(const ConvDesc* d, const void* dz, const void* y, const f
   return -1;
 }
 
-// Gram = a^T a and s = sum_p a_p of a = relu(sc*y + sh) (y [Nb,H,W,C] 16-bit; WGRAD_GRAM): slab
-// [splits][C + 1][C] -- per split the partial Gram, then the partial column sums as row C (one
-// split-K reduce gives both). Tiles (64, 64) two-stage, (-128, 128), (-128, 64); -1 otherwise.
 int pda_conv_wgrad_gram(const ConvDesc* d, const void* y, const float* sc, const float* sh,
                         float* slab, int splits, int k_chunk, int dt, int bm, int bn, hipStream_t st) {
   if (dt != DT_BF16 && dt != DT_F16) return -1;
@@ -2196,7 +2167,6 @@ int pda_conv_wgrad_gram(const ConvDesc* d, const void* y, const float* sc, const
   return -1;
 }
 
-// B = W Gram (f32 [Cout][C]); W 16-bit [Cout][C], Gram f32 [C][C]. C a multiple of 4.
 int pda_fold_bgemm(const void* w, const float* gram, int Cout, int C, float* b, int dt, hipStream_t st) {
   if (C % 4) return -2;
   const dim3 grid((Cout * (C / 4) + 255) / 256);
@@ -2209,7 +2179,6 @@ int pda_fold_bgemm(const void* w, const float* gram, int Cout, int C, float* b, 
   return (int)hipGetLastError();
 }
 
-// slab[splits][Cout][R*S*Cin] partial weight gradients (f32). k_chunk must be a multiple of 64.
 int pda_conv_wgrad(const ConvDesc* d, const void* dy, const void* x, float* slab, int splits,
                    int k_chunk, const float* pro_sc, const float* pro_sh, int dt, int bm, int bn,
                    hipStream_t st) {
@@ -2228,14 +2197,6 @@ int pda_conv_wgrad(const ConvDesc* d, const void* dy, const void* x, float* slab
   return dispatch<WGRAD>(dt, bm, bn, p, dim3(tiles, splits), st);
 }
 
-// Host-side descriptor of one queued reduction (mirrors ops/ext.py RedDescC).
-struct RedDescC {
-  const float* slab; float* grad; const float* ck; const float* cB; const float* cs;
-  int splits, M, N, cin_log2, cin_real, pitch, accumulate;
-  float scale;
-};
-
-// n (<= 24) split-K reductions of pda_wgrad_reduce's kind, N % 4 == 0 each, in one launch.
 int pda_wgrad_reduce_batch(const RedDescC* ds, int n, hipStream_t st) {
   if (n <= 0) return 0;
   if (n > RB_MAX) return -2;

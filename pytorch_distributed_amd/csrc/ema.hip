@@ -17,19 +17,12 @@
 // num_batches_tracked counters ride along as pairs of words). Elements outside every range are
 // neither read nor written. No atomics; every element is owned by one lane, so runs repeat bit for bit.
 #include "common.h"
+#include "pda_api.h"
 
 #include <algorithm>
 #include <cmath>
 #include <utility>
 #include <vector>
-
-struct EmaRange {        // mirrored by ops/native_ops.py EmaRange
-  void* e;
-  void* p;
-  void* shadow;          // 16-bit shadow of p (EMA_SWAP), or null
-  long long count;       // elements (4 bytes each)
-};
-static_assert(sizeof(EmaRange) == 32, "range rows are mirrored in Python");
 
 namespace {
 
@@ -121,11 +114,6 @@ __global__ __launch_bounds__(NT) void ema_kernel(const EmaTable t, float w, int 
 
 extern "C" {
 
-// Host-side validation of a range table. 0 = good; otherwise the negative code that
-// ops/native_ops.py turns into a ValueError:
-//  -1 bad row count / mode / shadow dtype, or a null e or p, -2 a range start that is not 16-byte
-//  aligned (8-byte for the shadow), -3 a negative count (or more than 2^31 - 1 blocks), -4 two of
-//  the e, p and shadow ranges overlap, -5 w not finite or outside [0, 1]
 int pda_ema_check(const EmaRange* rows, int nrows, int mode, float w, int dt) {
   if (nrows < 0 || (nrows && !rows) || mode < EMA_LERP || mode > EMA_SWAP) return -1;
   if (!std::isfinite(w) || w < 0.f || w > 1.f) return -5;
@@ -154,8 +142,6 @@ int pda_ema_check(const EmaRange* rows, int nrows, int mode, float w, int dt) {
 
 int pda_ema_chunk() { return EMA_CHUNK; }
 
-// One pass of `mode` over the ranges, on stream st: the whole table is validated first, then every
-// EMA_MAX_ROWS non-empty ranges go out as one launch (the model's two ranges: one launch).
 int pda_ema(const EmaRange* rows, int nrows, int mode, float w, int dt, hipStream_t st) {
   const int rc = pda_ema_check(rows, nrows, mode, w, dt);
   if (rc) return rc;

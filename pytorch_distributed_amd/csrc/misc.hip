@@ -13,6 +13,7 @@
 //   synth_nhwc8    : on-device synthetic ImageNet batch: NHWC, 3 channels padded to 8, 16-bit,
 //                    bit-compatible with data/synthetic.py (label + uniform u) (K12)
 #include "common.h"
+#include "pda_api.h"
 
 namespace {
 
@@ -396,16 +397,12 @@ thread_local unsigned long long g_trk_count = 0;
 
 extern "C" {
 
-// Arm (ev != null) / disarm fork tracking of this host thread's launches on stream st (common.h).
 int pda_track(hipStream_t st, hipEvent_t ev) {
   g_trk_stream = st;
   g_trk_event = ev;
   return 0;
 }
 unsigned long long pda_track_count() { return g_trk_count; }
-int pda_event_create(hipEvent_t* ev) { return (int)hipEventCreateWithFlags(ev, hipEventDisableTiming); }
-// flags: hipEventDisableTiming | optionally hipEventDisableSystemFence (the fork events are only
-// waited on by a stream of the same device: an agent-scope release is enough)
 int pda_event_create_flags(hipEvent_t* ev, unsigned flags) { return (int)hipEventCreateWithFlags(ev, flags); }
 int pda_event_record(hipEvent_t ev, hipStream_t st) { return (int)hipEventRecord(ev, st); }
 int pda_event_destroy(hipEvent_t ev) { return (int)hipEventDestroy(ev); }
@@ -430,7 +427,6 @@ int pda_xent(const float* logits, int B, int K, int ld_in, const long long* labe
   return (int)hipGetLastError();
 }
 
-// loss = mean(loss_rows) alone: the second launch of pda_xent, for the soft-target loss (mix.hip)
 int pda_mean_rows(const float* v, int n, float* out, hipStream_t st) {
   TRACKED_LAUNCH(mean_kernel, dim3(1), dim3(1024), 0, st, v, n, out);
   return (int)hipGetLastError();

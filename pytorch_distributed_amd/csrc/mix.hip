@@ -12,9 +12,7 @@
 //                no atomics; a lane whose chunk lies wholly on one side of the box loads only
 //                that side.
 #include "common.h"
-
-// loss = mean(loss_rows): mean_kernel's launch (misc.hip)
-extern "C" int pda_mean_rows(const float* v, int n, float* out, hipStream_t st);
+#include "pda_api.h"
 
 namespace {
 
@@ -216,11 +214,6 @@ int pda_xent_soft(const float* logits, int B, int K, int ld_in, const long long*
   return (int)hipGetLastError();
 }
 
-// layout 0 = s2d (dt f32 / bf16 / f16, S even), 1 = NCHW f32. Returns -2 for arguments the kernels
-// must never see (the Python wrapper refuses them first, with a message), pointers that are not
-// 16-byte aligned among them, in either layout. ``grid_cap``: the most blocks to launch (0: 65536;
-// the kernels stride over what a smaller grid leaves) -- the wrapper always passes 0, the tests
-// call this entry point with a small cap to make both grid-stride loops iterate at small shapes.
 int pda_batch_mix(const void* x, void* out, int B, int S, int dt, int layout, int mode, float lam,
                   float oml, int y1, int y2, int x1, int x2, int grid_cap, hipStream_t st) {
   if (B < 1 || S < 1 || S > 32768 || x == out || x == nullptr || out == nullptr) return -2;

@@ -15,21 +15,10 @@
 // Elements of p, g, buf and the shadow outside every segment are neither read nor written. The
 // launchers validate both tables on the host (pda_seg_check); the kernels then trust them.
 #include "common.h"
+#include "pda_api.h"
 
 #include <algorithm>
 #include <vector>
-
-struct SegRow {          // mirrored by ops/native_ops.py SEG_ROW
-  long long off, numel;
-  float lr, momentum, wd, trust, eps;
-  int flags;             // bit0 = Nesterov
-  int blk0, nblk;        // the segment's blocks: [blk0, blk0 + nblk) of the block table
-};
-struct BlkRow {          // mirrored by ops/native_ops.py BLK_ROW
-  long long first;       // flat index of the chunk's first element (a multiple of 4)
-  int seg, count;
-};
-static_assert(sizeof(SegRow) == 48 && sizeof(BlkRow) == 16, "table rows are mirrored in Python");
 
 namespace {
 
@@ -165,11 +154,6 @@ __global__ __launch_bounds__(NT) void sgd_seg_kernel(float* __restrict__ p, cons
 
 extern "C" {
 
-// Host-side validation of a segment table and its block table against a flat buffer of n elements.
-// 0 = good; otherwise the negative code that ops/native_ops.py turns into a ValueError:
-//  -1 counts / pointers, -2 offset not a multiple of 4 or negative, -3 segment empty or past n,
-//  -4 overlapping segments, -5 hyper-parameter not finite or negative, -6 block table does not cover
-//  every segment exactly once in chunks of at most SEG_CHUNK elements
 int pda_seg_check(const SegRow* segs, int nseg, const BlkRow* blks, int nblk, long long n) {
   if (nseg < 0 || nblk < 0 || n < 0 || (nseg && !segs) || (nblk && !blks)) return -1;
   std::vector<std::pair<long long, long long>> span;
@@ -204,8 +188,6 @@ int pda_seg_check(const SegRow* segs, int nseg, const BlkRow* blks, int nblk, lo
 
 int pda_seg_chunk() { return SEG_CHUNK; }
 
-// slab: 2 * nblk doubles. *_host tables are validated, *_dev tables (the same bytes) are read by
-// the kernel.
 int pda_seg_norms(const float* p, const float* g, long long n, const void* seg_dev, const void* blk_dev,
                   const void* seg_host, const void* blk_host, int nseg, int nblk, double* slab,
                   hipStream_t st) {

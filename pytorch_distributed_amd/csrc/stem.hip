@@ -22,6 +22,7 @@
 // halving butterfly over its lanes), so the tile loop has no barrier besides the slab's.
 // Fixed reduction order: deterministic.
 #include "common.h"
+#include "pda_api.h"
 
 #include <type_traits>
 
@@ -213,9 +214,6 @@ int launch_stem(const void* x, const void* w, void* y, float* stats, int Nb, int
 
 }  // namespace
 
-// y [Nb][H][W][64] = conv4x4/1 (pad 2 top/left) of x [Nb][H][W][16] with w [64][256] (K order
-// tap-major, channel-minor), 16-bit; stats (nullable) [Nb*H][3][64] shifted partials per output
-// row (W rows of M). Requires H % 4 == 0, W % 16 == 0, W <= 128; returns -1 otherwise.
 extern "C" int pda_stem_fwd(const void* x, const void* w, void* y, float* stats, int Nb, int H, int W,
                             int dt, int grid_cap, hipStream_t st) {
   if (Nb <= 0 || H <= 0 || H % ST_TH || W % 16 || W < 16 || W > 128 || (dt != DT_BF16 && dt != DT_F16))

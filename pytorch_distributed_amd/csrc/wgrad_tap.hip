@@ -26,6 +26,7 @@
 // one co row, stored as f32x4 into the split-K slab [split][Cout][9 Cin] that pda_wgrad_reduce sums.
 // Wave (wr, wc): co rows 32 wr .. +32, columns 144 wc .. +144 of the 576 = 9 taps x 64 ci.
 #include "common.h"
+#include "pda_api.h"
 
 namespace {
 
@@ -549,11 +550,6 @@ FastDiv wt_div(uint32_t d) {
 
 extern "C" {
 
-// Split-K weight-gradient slabs of a 3x3 / stride-1 / pad-1 convolution, tap-reuse form:
-// slab [splits][Cout][9 Cin] (f32) -- pda_wgrad_reduce sums them like the generic kernel's.
-// dy [Nb,H,W,Cout], x [Nb,H,W,Cin] 16-bit; pro_sc / pro_sh: BN+ReLU of a PRE-BatchNorm x (or null).
-// kb: padded rows per split (multiple of 64); splits = ceil(Nb (H+2)(W+2) / kb). Cin, Cout multiples
-// of 64; W <= 59 (the X ring holds 4 steps + the two halos). Returns -2 on a shape it does not take.
 int pda_wgrad_tap(const void* dy, const void* x, float* slab, const float* pro_sc,
                   const float* pro_sh, int Nb, int H, int W, int Cin, int Cout, int kb, int splits,
                   int dt, hipStream_t st) {
@@ -586,10 +582,6 @@ int pda_wgrad_tap(const void* dy, const void* x, float* slab, const float* pro_s
   return (int)hipGetLastError();
 }
 
-// The stem's weight-gradient slabs in the tap-reuse form (wgrad_stem_tap_kernel): slab
-// [splits][64][16 taps x 16] (f32), summed by pda_wgrad_reduce as the generic kernel's. dz, y
-// [Nb,H,W,64], x [Nb,H,W,16] 16-bit, k [3][64]. kb: padded rows per split (multiple of 64);
-// splits = ceil(Nb (H+3)(W+3) / kb). W + 3 <= 122 (the X ring holds 4 steps + the forward halo).
 int pda_wgrad_stem_tap(const void* dz, const void* y, const float* k, const void* x, float* slab,
                        int Nb, int H, int W, int kb, int splits, int dt, hipStream_t st) {
   if (kb <= 0 || (kb % 64) || H <= 0 || W <= 0 || W + 3 > 122 || !dz || !y || !k || !x || !slab)

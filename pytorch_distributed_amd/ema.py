@@ -93,8 +93,8 @@ class _EMABase:
 
 
 class NativeEMA(_EMABase):
-    """EMA of a :class:`~pytorch_distributed_amd.models.native.NativeResNet`: ``ema_params`` mirrors
-    ``flat_params`` and ``ema_bufstore`` mirrors ``flat_bufstore`` (running mean / var, then the
+    """EMA of a :class:`~pytorch_distributed_amd.models.native.NativeResNet`: ``ema_params`` follows
+    ``flat_params`` and ``ema_bufstore`` follows ``flat_bufstore`` (running mean / var, then the
     ``num_batches_tracked`` counters). ``update()`` is one launch over (parameters, statistics) and
     a copy of the counters: no host synchronisation, no allocation."""
 

@@ -764,7 +764,7 @@ class NativeResNet(nn.Module):
         if (not self.fork_tracking or self._side is None or self.defer_side
                 or getattr(self.ws, "sync_comm", None) is not None
                 or torch.cuda.is_current_stream_capturing()
-                or getattr(L, "pda_track", None) is None):
+                or not ext.has("pda_track")):
             return
         if self._trk_ev is None:
             self._trk_ev = K.fork_event_create()

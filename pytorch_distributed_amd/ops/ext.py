@@ -2,24 +2,30 @@
 
 The library exposes a C ABI of launchers that take raw device pointers and a
 ``hipStream_t``; no torch headers are compiled, so the build is fast and
-ABI-independent of the PyTorch wheel. Every launcher returns the HIP error
-code of the launch, which :func:`_check` turns into an exception -- ops never
-fall back silently to PyTorch on a GPU box (a missing library raises).
+ABI-independent of the PyTorch wheel. That ABI is declared once, in
+``csrc/pda_api.h``: the compiler holds every definition to it, and :func:`load`
+binds ``argtypes`` / ``restype`` from the same text (:func:`read_api`). Every
+launcher returns the HIP error code of the launch, which :func:`check` turns into
+an exception -- ops never fall back silently to PyTorch on a GPU box (a missing
+library raises).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from pathlib import Path
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
 
-__all__ = ["load", "available", "lib", "DT", "dt_of", "ConvDesc", "BwdArgs", "BnEpi", "BnFwdOut", "BnBwdOut",
-           "stream", "ptr"]
+__all__ = ["load", "available", "lib", "has", "DT", "dt_of", "ConvDesc", "BwdArgs", "BnEpi", "BnFwdOut",
+           "BnBwdOut", "RedDescC", "SegRow", "BlkRow", "EmaRange", "stream", "ptr"]
 
-_LIB: Optional[C.CDLL] = None
+_LIB: Optional[SimpleNamespace] = None
 _ERR: Optional[str] = None
+API_H = Path(__file__).resolve().parent.parent / "csrc" / "pda_api.h"
 LIBPATH = Path(__file__).resolve().parent.parent / "_lib" / "libpda_kernels.so"
 if os.environ.get("PDA_KERNEL_LIB"):   # A/B variants (tools/build_variant.py), relative to _lib/
     LIBPATH = LIBPATH.parent / os.environ["PDA_KERNEL_LIB"]
@@ -31,12 +37,15 @@ def dt_of(t) -> int:
     return DT[t if isinstance(t, torch.dtype) else t.dtype]
 
 
+# ------------------------------------------------------------------ the structs of csrc/pda_api.h
+# (field for field; tests/test_abi_cpu.py holds each layout to the header's static_asserts)
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("Nb", "H", "W", "Cin", "Cout", "R", "S", "stride", "pad", "Ho", "Wo")]
 
 
 class BwdArgs(C.Structure):
+    """``BwdArgsC``: arguments of pda_bn_bwd_reduce / pda_bn_bwd_apply."""
     _fields_ = [("g1", C.c_void_p), ("g2", C.c_void_p), ("gp", C.c_void_p), ("HW", C.c_int),
                 ("y", C.c_void_p), ("sc", C.c_void_p), ("sh", C.c_void_p),
                 ("y2", C.c_void_p), ("sc2", C.c_void_p), ("sh2", C.c_void_p),
@@ -53,7 +62,7 @@ class BnEpi(C.Structure):
 
 
 class BnFwdOut(C.Structure):
-    """Outputs of the one-launch BatchNorm forward statistics (csrc/bn.hip bn_fwd_stats)."""
+    """Outputs of the one-launch BatchNorm forward statistics (csrc/bn.hip bn_stats_kernel<0>)."""
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p),
                 ("eps", C.c_float), ("momentum", C.c_float),
                 ("mean", C.c_void_p), ("invstd", C.c_void_p), ("scale", C.c_void_p),
@@ -70,82 +79,78 @@ class BnBwdOut(C.Structure):
 
 
 class RedDescC(C.Structure):
-    """One split-K reduction of pda_wgrad_reduce_batch (csrc/conv_gemm.hip RedDescC)."""
+    """One split-K reduction of pda_wgrad_reduce_batch."""
     _fields_ = [("slab", C.c_void_p), ("grad", C.c_void_p), ("ck", C.c_void_p), ("cB", C.c_void_p),
                 ("cs", C.c_void_p)] + [(n, C.c_int) for n in
                                        ("splits", "M", "N", "cin_log2", "cin_real", "pitch",
                                         "accumulate")] + [("scale", C.c_float)]
 
 
-_V, _I, _F, _L, _U, _D = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_uint, C.c_double
-_SIGS = {
-    "pda_conv_fwd": [C.POINTER(ConvDesc), _V, _V, _I, _V, _I, _I, _V, _V, _I, _V, _V, _I, _I, _I, _V],
-    "pda_conv_fwd_tail": [C.POINTER(ConvDesc), _V, _V, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I,
-                          _I, _I, _V],
-    "pda_conv_dgrad": [C.POINTER(ConvDesc), _V, _V, _V, C.POINTER(BnEpi), _I, _I, _I, _V],
-    "pda_conv_dgrad_bnf": [C.POINTER(ConvDesc), _V, _V, _V, C.POINTER(BnEpi), _V, _V, _V, _V, _I, _I,
-                           _I, _V],
-    "pda_bn_fold": [_V, _V, _I, _I, _V, _V, _I, _V],
-    "pda_wgrad_tap": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
-    "pda_wgrad_stem_tap": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
-    "pda_stem_fwd": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
-    "pda_conv_wgrad": [C.POINTER(ConvDesc), _V, _V, _V, _I, _I, _V, _V, _I, _I, _I, _V],
-    "pda_conv_wgrad_bna": [C.POINTER(ConvDesc), _V, _V, _V, _V, _V, _V, _V, _I, _I, _V, _V, _I, _I, _I,
-                           _V],
-    "pda_wgrad_reduce": [_V, _V, _I, _I, _I, _I, _I, _I, _F, _I, _V, _V, _V, _V],
-    "pda_wgrad_reduce_batch": [C.POINTER(RedDescC), _I, _V],
-    "pda_conv_wgrad_gram": [C.POINTER(ConvDesc), _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
-    "pda_fold_bgemm": [_V, _V, _I, _I, _V, _I, _V],
-    "pda_bn_fwd_stats": [_V, _I, _I, _I, _I, _I, _V, _V, C.POINTER(BnFwdOut), _I, _V],
-    "pda_bn_bwd_stats": [_V, _I, _I, _I, _I, _V, _V, C.POINTER(BnBwdOut), _I, _V],
-    "pda_bn_finalize_tot": [_V, _I, _D, _V, _V, _F, _F, _V, _V, _V, _V, _V, _V, _V, _I, _V],
-    "pda_slab_reduce": [_V, _I, _I, _I, _V, _V],
-    "pda_bn_eval_coeffs": [_V, _V, _V, _V, _F, _I, _V, _V, _V],
-    "pda_bn_apply": [_V, _V, _V, _V, _V, _V, _V, _L, _I, _I, _I, _V, _I, _V],
-    "pda_stem_pool": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V],
-    "pda_maxpool_bwd": [_V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V],
-    "pda_tail_pool": [_V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
-    "pda_bn_bwd_reduce": [C.POINTER(BwdArgs), _I, _I, _V],
-    "pda_stem_bwd_reduce": [_V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _I, _V],
-    "pda_bn_bwd_finalize": [_V, _I, _I, _I, _I, _F, _V, _V, _V, _V, _V, _V, _V, _V, _F, _I, _V],
-    "pda_bn_bwd_apply": [C.POINTER(BwdArgs), _V, _V, _V, _V, _V, _V, _I, _V],
-    "pda_xent": [_V, _I, _I, _I, _V, _V, _V, _V, _I, _F, _V, _I, _I, _V],
-    "pda_xent_soft": [_V, _I, _I, _I, _V, _V, _F, _F, _V, _V, _V, _I, _F, _V, _I, _I, _V],
-    "pda_mean_rows": [_V, _I, _V, _V],
-    "pda_batch_mix": [_V, _V, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _I, _V],
-    "pda_topk": [_V, _I, _I, _I, _V, _V, _V],
-    "pda_col_sum": [_V, _I, _I, _I, _F, _V, _I, _I, _V],
-    "pda_sgd_flat": [_V, _V, _V, _V, _L, _F, _F, _F, _V, _V, _I, _I, _V],
-    "pda_cast_flat": [_V, _V, _L, _I, _V],
-    "pda_amp_scan": [_V, _L, _V, _V, _V, _V, _V, _F, _F, _I, _V],
-    "pda_pack_stem": [_V, _V, _I, _I, _I, _I, _I, _I, _V],
-    "pda_synth": [_V, _I, _U, _I, _V, _V, _I, _V, _I, _V],
-    "pda_synth_s2d": [_V, _I, _U, _I, _V, _V, _I, _V, _I, _V],
-    "pda_nchw_to_s2d": [_V, _I, _I, _I, _V, _I, _V],
-    "pda_aug_resize": [_V, _V, _V, _I, _I, _V, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _V],
-    "pda_aug_resize_fmt": [_V, _V, _V, _I, _I, _V, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                           _V],
-    "pda_aug_draw": [_V, _V, _V, _I, _L, _U, _I, _U, _I, _I, _I, _D, _D, _D, _D, _V, _V, _V, _V],
-    "pda_pack_stem_s2d": [_V, _V, _I, _I, _V],
-    "pda_stem_s2d_grad": [_V, _V, _I, _I, _V],
-    "pda_set_stream_cfg": [_I, _I, _I, _I],
-    "pda_fork_probe": [_V, _V, _I, _V, _V],
-    "pda_track": [_V, _V],
-    "pda_track_count": [],
-    "pda_event_create": [_V],
-    "pda_event_create_flags": [_V, _U],
-    "pda_event_record": [_V, _V],
-    "pda_event_destroy": [_V],
-    "pda_stream_wait_event": [_V, _V],
-    "pda_bn_bwd_apply2": [_V, _V, _V, _V, _V, _V, _L, _I, _I, _V],
-    "pda_seg_check": [_V, _I, _V, _I, _L],
-    "pda_seg_chunk": [],
-    "pda_seg_norms": [_V, _V, _L, _V, _V, _V, _V, _I, _I, _V, _V],
-    "pda_sgd_seg": [_V, _V, _V, _V, _L, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _V],
-    "pda_ema_check": [_V, _I, _I, _F, _I],
-    "pda_ema_chunk": [],
-    "pda_ema": [_V, _I, _I, _F, _I, _V],
-}
+class SegRow(C.Structure):
+    """One parameter tensor's range of the flat buffers and its hyper-parameters (csrc/optim.hip)."""
+    _fields_ = [("off", C.c_longlong), ("numel", C.c_longlong), ("lr", C.c_float),
+                ("momentum", C.c_float), ("wd", C.c_float), ("trust", C.c_float), ("eps", C.c_float),
+                ("flags", C.c_int), ("blk0", C.c_int), ("nblk", C.c_int)]
+
+
+class BlkRow(C.Structure):
+    """One block's chunk: ``count`` <= SEG_CHUNK elements of segment ``seg`` from flat index ``first``."""
+    _fields_ = [("first", C.c_longlong), ("seg", C.c_int), ("count", C.c_int)]
+
+
+class EmaRange(C.Structure):
+    """One (e, p[, 16-bit shadow of p]) range of ``count`` 4-byte elements (csrc/ema.hip)."""
+    _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("shadow", C.c_void_p), ("count", C.c_longlong)]
+
+
+STRUCTS = {"ConvDesc": ConvDesc, "BwdArgsC": BwdArgs, "BnEpi": BnEpi, "BnFwdOut": BnFwdOut,
+           "BnBwdOut": BnBwdOut, "RedDescC": RedDescC, "SegRow": SegRow, "BlkRow": BlkRow,
+           "EmaRange": EmaRange}
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "float": C.c_float, "double": C.c_double,
+            "long long": C.c_longlong, "unsigned long long": C.c_ulonglong}
+_HANDLES = ("hipStream_t", "hipEvent_t")
+
+
+# ------------------------------------------------------------------ reading csrc/pda_api.h
+def _ctype(decl: str):
+    """The ctypes type of one named parameter (``const float* x``) in the header's restricted style."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    base, stars = " ".join(w for w in words[:-1] if w != "*"), words[:-1].count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base in _HANDLES:
+        return C.c_void_p
+    if stars == 1 and base in STRUCTS:
+        return C.POINTER(STRUCTS[base])
+    if stars == 1 and (base in _SCALARS or base in _HANDLES or base == "void"):
+        return C.c_void_p
+    raise ValueError(f"pda_api.h: parameter {decl!r} is outside the types the header may use")
+
+
+def _code(text: str) -> str:
+    return re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+
+
+def read_api(text: str) -> dict:
+    """``{name: (restype, [argtypes])}`` of every ``pda_*`` prototype in the header text."""
+    api = {}
+    for ret, name, params in re.findall(r"^[ \t]*(\w[\w ]*?) +(pda_\w+)\(([^)]*)\);", _code(text), re.M):
+        if ret not in _SCALARS:
+            raise ValueError(f"pda_api.h: {name} returns {ret!r}")
+        api[name] = (_SCALARS[ret], [_ctype(p) for p in params.split(",") if p.strip()])
+    return api
+
+
+def read_layouts(text: str) -> dict:
+    """``{struct: (sizeof, last field, its offset)}`` from the header's static_asserts."""
+    code = _code(text)
+    size = dict(re.findall(r"static_assert\(sizeof\((\w+)\) == (\d+)", code))
+    return {s: (int(size[s]), f, int(o))
+            for s, f, o in re.findall(r"static_assert\(offsetof\((\w+), (\w+)\) == (\d+)", code)}
+
+
+def api_text() -> str:
+    return API_H.read_text()
 
 
 def stream_cfg() -> tuple:
@@ -159,7 +164,9 @@ def stream_cfg() -> tuple:
     return (-1, 3, 65536, 50)
 
 
-def load(required: bool = False) -> Optional[C.CDLL]:
+def load(required: bool = False) -> Optional[SimpleNamespace]:
+    """The bound library: a namespace holding exactly the functions pda_api.h declares, so a name it
+    does not declare fails in Python (AttributeError) instead of reaching C without ``argtypes``."""
     global _LIB, _ERR
     if _LIB is not None:
         return _LIB
@@ -170,20 +177,24 @@ def load(required: bool = False) -> Optional[C.CDLL]:
         except Exception as e:  # pragma: no cover
             _ERR = f"build failed: {e}"
     try:
-        lib = C.CDLL(str(LIBPATH))
-        for name, argt in _SIGS.items():
-            fn = getattr(lib, name, None)
-            if fn is None:   # an older A/B variant library (tools/build_variant.py)
-                continue
-            fn.argtypes = argt
-            fn.restype = C.c_int
-        if getattr(lib, "pda_set_stream_cfg", None) is not None:
-            lib.pda_set_stream_cfg(*stream_cfg())
-        _LIB = lib
+        dll = C.CDLL(str(LIBPATH))
     except OSError as e:
         _ERR = str(e)
         if required:
             raise RuntimeError(f"native kernels unavailable: {_ERR}") from e
+        return None
+    lib = SimpleNamespace()
+    for name, (restype, argtypes) in read_api(api_text()).items():
+        fn = getattr(dll, name, None)
+        if fn is None:
+            if os.environ.get("PDA_KERNEL_LIB"):   # an A/B variant library may hold a subset
+                continue
+            raise RuntimeError(f"{LIBPATH} lacks {name}, which csrc/pda_api.h declares: rebuild it")
+        fn.argtypes, fn.restype = argtypes, restype
+        setattr(lib, name, fn)
+    if hasattr(lib, "pda_set_stream_cfg"):
+        lib.pda_set_stream_cfg(*stream_cfg())
+    _LIB = lib
     return _LIB
 
 
@@ -191,10 +202,15 @@ def available() -> bool:
     return load() is not None
 
 
-def lib() -> C.CDLL:
+def lib() -> SimpleNamespace:
     l = load(required=True)
     assert l is not None
     return l
+
+
+def has(name: str) -> bool:
+    """Whether the loaded library has ``name`` (an A/B variant library may lack some launchers)."""
+    return hasattr(lib(), name)
 
 
 def stream(device=None) -> int:

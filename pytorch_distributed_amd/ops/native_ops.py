@@ -21,7 +21,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ext
-from .ext import ConvDesc, BwdArgs, check, dt_of, ptr, stream
+from .ext import BlkRow, BwdArgs, ConvDesc, EmaRange, SegRow, check, dt_of, ptr, stream
 
 __all__ = [
     "ConvGeom", "conv_fwd", "conv_dgrad", "conv_wgrad", "pick_tile", "fwd_tile", "wgrad_plan",
@@ -40,7 +40,7 @@ class ConvGeom:
     Nb: int
     H: int
     W: int
-    Cin: int     # channels of the stored input (stem: 8, padded from 3)
+    Cin: int     # channels of the stored input (stem: 16, the 2x2 space-to-depth image)
     Cout: int
     R: int
     S: int
@@ -304,7 +304,7 @@ def tail_fuse_ok(g: ConvGeom, dtype: torch.dtype) -> bool:
     stride-1 conv without padding on 16-bit operands, Cin a multiple of 64."""
     return (dtype in (torch.bfloat16, torch.float16) and g.R == 1 and g.S == 1 and g.stride == 1
             and g.pad == 0 and g.Cin % 64 == 0
-            and getattr(ext.lib(), "pda_conv_fwd_tail", None) is not None)
+            and ext.has("pda_conv_fwd_tail"))
 
 
 def _conv_fwd_tail(y3, w, g: ConvGeom, out, pro, tail: TailIn, stats, bn, before_finalize):
@@ -347,7 +347,7 @@ def stem_fwd_ok(g: ConvGeom, dtype: torch.dtype) -> bool:
     return (_STEM_FWD and dtype in (torch.bfloat16, torch.float16) and g.R == 4 and g.S == 4
             and g.Cin == 16 and g.Cout == 64 and g.stride == 1 and g.pad == 2 and g.Ho == g.H
             and g.Wo == g.W and g.H % 4 == 0 and g.W % 16 == 0 and 16 <= g.W <= 128
-            and getattr(ext.lib(), "pda_stem_fwd", None) is not None)
+            and ext.has("pda_stem_fwd"))
 
 
 def stem_fwd(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: torch.Tensor,
@@ -505,7 +505,7 @@ def bnf_ok(g: ConvGeom, dtype: torch.dtype) -> bool:
     conv without padding, 16-bit operands, channel counts in whole 64-column panels."""
     return (g.R == 1 and g.S == 1 and g.pad == 0 and dtype in (torch.bfloat16, torch.float16)
             and g.Cin % 64 == 0 and g.Cout % 64 == 0
-            and getattr(ext.lib(), "pda_conv_dgrad_bnf", None) is not None)
+            and ext.has("pda_conv_dgrad_bnf"))
 
 
 def conv_dgrad_bnf(dz: torch.Tensor, wf: torch.Tensor, g: ConvGeom, dx: torch.Tensor,
@@ -653,7 +653,7 @@ def wgrad_bna_ok(g: ConvGeom, Nb: int, dtype: torch.dtype) -> bool:
     operands on the tiles WGRAD_BNA is built for (64x128, 64x256: the stem's Cout = 64)."""
     if dtype not in (torch.bfloat16, torch.float16) or g.Cout % 8:
         return False
-    if getattr(ext.lib(), "pda_conv_wgrad_bna", None) is None:
+    if not ext.has("pda_conv_wgrad_bna"):
         return False
     bm, bn, _, _ = wgrad_plan(g, Nb, bna=True)
     return (abs(bm), bn) in _BNA_TILES
@@ -745,7 +745,7 @@ def wgrad_tap_ok(g: ConvGeom, dtype: torch.dtype) -> bool:
     return (dtype in (torch.bfloat16, torch.float16) and g.R == 3 and g.S == 3 and g.stride == 1
             and g.pad == 1 and g.Ho == g.H and g.Wo == g.W and g.W <= 59 and g.W in _WGRAD_TAP
             and g.Cin % 64 == 0 and g.Cout % 64 == 0 and (g.Cin & (g.Cin - 1)) == 0
-            and getattr(ext.lib(), "pda_wgrad_tap", None) is not None)
+            and ext.has("pda_wgrad_tap"))
 
 
 def wgrad_tap_plan(g: ConvGeom, Nb: int, blocks: int = _WGRAD_TAP_BLOCKS) -> Tuple[int, int]:
@@ -813,7 +813,7 @@ def stem_wgrad_tap_ok(g: ConvGeom, dtype: torch.dtype, force: bool = False) -> b
     return ((force or _STEM_WGRAD == "tap") and dtype in (torch.bfloat16, torch.float16) and g.R == 4
             and g.S == 4 and g.stride == 1 and g.pad == 2 and g.Cin == 16 and g.Cout == 64
             and g.Ho == g.H and g.Wo == g.W and g.W + 3 <= 122
-            and getattr(ext.lib(), "pda_wgrad_stem_tap", None) is not None)
+            and ext.has("pda_wgrad_stem_tap"))
 
 
 def conv_wgrad_stem_tap(dz: torch.Tensor, y: torch.Tensor, k: torch.Tensor, x: torch.Tensor,
@@ -1256,18 +1256,6 @@ SEG_CHUNK = 4096      # elements one block of seg_norms / sgd_seg handles (csrc/
 SEG_NESTEROV = 1      # SegRow.flags
 
 
-class SegRow(C.Structure):
-    """One parameter tensor's range of the flat buffers and its hyper-parameters (csrc/optim.hip)."""
-    _fields_ = [("off", C.c_longlong), ("numel", C.c_longlong), ("lr", C.c_float),
-                ("momentum", C.c_float), ("wd", C.c_float), ("trust", C.c_float), ("eps", C.c_float),
-                ("flags", C.c_int), ("blk0", C.c_int), ("nblk", C.c_int)]
-
-
-class BlkRow(C.Structure):
-    """One block's chunk: ``count`` <= SEG_CHUNK elements of segment ``seg`` from flat index ``first``."""
-    _fields_ = [("first", C.c_longlong), ("seg", C.c_int), ("count", C.c_int)]
-
-
 _SEG_ERRORS = {-1: "bad counts or a missing buffer", -2: "a segment offset is negative or no multiple of 4",
                -3: "a segment is empty or ends past the flat buffer", -4: "segments overlap",
                -5: "a hyper-parameter is negative or not finite",
@@ -1403,11 +1391,6 @@ EMA_CHUNK = 4096                          # elements one block of the EMA kernel
 EMA_LERP, EMA_COPY, EMA_SWAP = 0, 1, 2    # csrc/ema.hip EmaMode
 
 
-class EmaRange(C.Structure):
-    """One (e, p[, 16-bit shadow of p]) range of ``count`` 4-byte elements (csrc/ema.hip)."""
-    _fields_ = [("e", C.c_void_p), ("p", C.c_void_p), ("shadow", C.c_void_p), ("count", C.c_longlong)]
-
-
 _EMA_ERRORS = {-1: "bad mode or shadow dtype, or a missing e / p buffer",
                -2: "a range does not start 16-byte aligned (8-byte for the shadow)",
                -3: "a negative element count", -4: "e, p and shadow ranges overlap",
@@ -1466,7 +1449,7 @@ def ema_update(ranges, mode: int, w: float = 0.0) -> None:
     if len(ranges.rows) == 0:
         return
     dt = dt_of(ranges.shadow_dtype) if ranges.shadow_dtype is not None else 1
-    rc = ext.lib().pda_ema(C.cast(ranges.rows, C.c_void_p), len(ranges.rows), int(mode), float(w), dt,
+    rc = ext.lib().pda_ema(ranges.rows, len(ranges.rows), int(mode), float(w), dt,
                            stream(ranges.device))
     if rc < 0:
         raise ValueError(f"ema_update: {_EMA_ERRORS.get(rc, f'bad ranges ({rc})')}")

@@ -157,8 +157,7 @@ def test_segment_tables_and_their_host_check():
         return t
 
     def chk(t, n):
-        return L.pda_seg_check(C.cast(t.seg_host, C.c_void_p), t.nseg, C.cast(t.blk_host, C.c_void_p),
-                               t.nblocks, n)
+        return L.pda_seg_check(t.seg_host, t.nseg, t.blk_host, t.nblocks, n)
 
     S = K.SEG_CHUNK
     t = tables([(0, 5), (8, S + 1), (3 * S, 3 * S + 5)])

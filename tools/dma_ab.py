@@ -36,6 +36,7 @@ def run(names, cases, rounds, reps):
     from pytorch_distributed_amd.ops import native_ops as K
     from tools.conv_bench import SHAPES
     libs = {}
+    os.environ.setdefault("PDA_KERNEL_LIB", "ab")   # the variants hold conv_gemm.hip only: bind what is there
     for n in names:
         ext._LIB = None
         ext.LIBPATH = (ext.LIBPATH.parent.parent / "_lib" / "libpda_kernels.so" if n == "main" else
