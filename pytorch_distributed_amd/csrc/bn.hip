@@ -1224,6 +1224,8 @@ static FastDiv make_div(uint32_t d) {
 int pda_bn_apply(const void* y, const float* sc, const float* sh, const void* r2, const float* sc2,
                  const float* sh2, void* out, long long numel, int C, int mode, int relu,
                  void* mask, int dt, hipStream_t st) {
+  // 8-channel chunks that never straddle a row: C % 8, whole rows
+  if (C < 8 || (C & 7) || numel < 0 || numel % C) return -2;
   if (numel / 8 >= (1ll << 31)) return -2;
   const int n8 = (int)(numel / 8);
   const int g = grid_for(n8);
@@ -1294,6 +1296,10 @@ static BwdArgs to_args(const BwdArgsC* c) {
 }
 
 int pda_bn_bwd_reduce(const BwdArgsC* c, int G, int dt, hipStream_t st) {
+  // the kernel walks a row in passes of min(C/8, 256) chunks without a tail check: C/8 <= 256 or
+  // a multiple of 256
+  if (!c || c->C < 8 || (c->C & 7) || (c->C > 2048 && c->C % 2048) || G <= 0 || c->rows <= 0)
+    return -2;
   BwdArgs a = to_args(c);
   a.rows_per_block = (a.rows + G - 1) / G;
 #define K(D) TRACKED_LAUNCH(bn_bwd_reduce_kernel<D>, dim3(G), dim3(NT), 0, st, a)
@@ -1330,7 +1336,8 @@ int pda_bn_bwd_finalize(const float* part, int G, int nq, int qy, int C, float c
 
 int pda_bn_bwd_apply2(const void* dz, const void* y, const void* y2, const float* k, void* dy,
                       void* dy2, long long rows, int C, int dt, hipStream_t st) {
-  if ((dt != DT_BF16 && dt != DT_F16) || (C & 7) || rows * (C / 8) >= (1ll << 31)) return -1;
+  if (C < 8 || (C & 7) || rows < 0) return -2;
+  if ((dt != DT_BF16 && dt != DT_F16) || rows * (C / 8) >= (1ll << 31)) return -1;
   const int n8 = (int)(rows * (C / 8));
   // streaming config as the one-branch pass (auto: 4 chunks + nontemporal for >= 100 MiB),
   // else one chunk per trip
@@ -1351,6 +1358,7 @@ int pda_bn_bwd_apply2(const void* dz, const void* y, const void* y2, const float
 
 int pda_bn_bwd_apply(const BwdArgsC* c, const void* dz_in, const void* ysel, const float* k1,
                      const float* k2, const float* k3, void* dy, int dt, hipStream_t st) {
+  if (!c || c->C < 8 || (c->C & 7) || c->rows < 0) return -2;
   BwdArgs a = to_args(c);
   const int g = grid_for(a.rows * (a.C / 8));
   if (dz_in && a.rows * (a.C / 8) < (1ll << 31)) {

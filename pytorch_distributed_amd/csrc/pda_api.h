@@ -180,7 +180,9 @@ int pda_bn_bwd_stats(const float* part, int T, int nq, int C, int S, double* sla
 int pda_bn_eval_coeffs(const float* gamma, const float* beta, const float* rm, const float* rv,
                        float eps, int C, float* scale, float* shift, hipStream_t st);
 // mask (nullable): one byte per 8 elements, bit e = (output element e > 0) -- lets the backward of an
-// identity-shortcut tail skip re-reading the residual to rebuild its ReLU mask
+// identity-shortcut tail skip re-reading the residual to rebuild its ReLU mask.
+// pda_bn_apply / pda_bn_bwd_apply / pda_bn_bwd_apply2 work on 8-channel chunks of whole rows: -2
+// (nothing launched) for C < 8, C % 8 != 0 or an element count that is no multiple of C.
 int pda_bn_apply(const void* y, const float* sc, const float* sh, const void* r2, const float* sc2,
                  const float* sh2, void* out, long long numel, int C, int mode, int relu,
                  void* mask, int dt, hipStream_t st);
@@ -191,7 +193,9 @@ int pda_maxpool_bwd(const void* dout, const void* dout2, const void* arg, void* 
 int pda_tail_pool(const void* y, const float* sc, const float* sh, const void* r2, const float* sc2,
                   const float* sh2, void* out, int N, int HW, int C, int mode, int dt,
                   hipStream_t st);
-// G = number of partial slabs to write; part must hold G*nq*C floats.
+// G = number of partial slabs to write; part must hold G*nq*C floats. -2 (nothing launched) for
+// C < 8, C % 8 != 0, C > 2048 that is no multiple of 2048 (the kernel's row passes of 256 chunks
+// have no tail check), G <= 0 or rows <= 0.
 int pda_bn_bwd_reduce(const BwdArgsC* c, int G, int dt, hipStream_t st);
 // stem backward reduce (maxpool gather + ReLU mask + dz store + partials [G][2][C])
 int pda_stem_bwd_reduce(const void* dout, const void* dout2, const void* arg, const void* y,

@@ -950,16 +950,36 @@ def bn_eval_coeffs(gamma, beta, rmean, rvar, eps, scale, shift) -> None:
     check(rc, "bn_eval_coeffs")
 
 
+def _bn_shape(what: str, y, reduce: bool = False) -> None:
+    """The stand-alone BatchNorm kernels (csrc/bn.hip) work on 8-channel chunks of whole rows; the
+    reduce walks a row in passes of 256 chunks with no tail check. ValueError otherwise (the C
+    launchers refuse the same shapes with -2)."""
+    C_ = y.shape[-1] if y.dim() else 0
+    if C_ < 8 or C_ % 8 or y.numel() % C_:
+        raise ValueError(f"{what}: shape {tuple(y.shape)} needs a channel count (last dimension) "
+                         f"that is a multiple of 8")
+    if reduce and (y.numel() == 0 or (C_ > 2048 and C_ % 2048)):
+        raise ValueError(f"{what}: shape {tuple(y.shape)} needs at least one row and a channel "
+                         f"count of at most 2048 or a multiple of 2048")
+
+
+def _bn_check(rc: int, what: str, y) -> None:
+    if rc == -2:
+        raise ValueError(f"{what}: shape {tuple(y.shape)} refused by the kernel library")
+    check(rc, what)
+
+
 def bn_apply(y, scale, shift, out, res=None, y2=None, scale2=None, shift2=None, relu=True,
              mask=None):
     """out = act(bn(y) [+ res | + bn2(y2)]); mask (uint8, numel/8) optionally receives the output's
     ReLU bitmask (bit e of byte i: element 8i+e > 0)."""
+    _bn_shape("bn_apply", y)
     mode = 2 if y2 is not None else (1 if res is not None else 0)
     r2 = y2 if y2 is not None else res
     rc = ext.lib().pda_bn_apply(ptr(y), ptr(scale), ptr(shift), ptr(r2), ptr(scale2), ptr(shift2),
                                 ptr(out), y.numel(), y.shape[-1], mode, int(relu), ptr(mask),
                                 dt_of(y), stream(y.device))
-    check(rc, "bn_apply")
+    _bn_check(rc, "bn_apply", y)
     return out
 
 
@@ -1023,6 +1043,7 @@ def bn_bwd(ws: Workspace, y, mean, invstd, gamma, scale, shift, dgamma, dbeta, d
     Writes dgamma/dbeta (f32, * gscale, optionally accumulated) and dy_out (16-bit).
     With a residual (``res`` or ``y2``) the masked gradient dz is materialised in ``dz_buf``
     because it is also the gradient of the shortcut input."""
+    _bn_shape("bn_bwd", y, reduce=True)
     N, H, W, C_ = y.shape
     rows = N * H * W
     mode = 3 if no_mask else (2 if y2 is not None else (1 if res is not None else 0))
@@ -1036,7 +1057,7 @@ def bn_bwd(ws: Workspace, y, mean, invstd, gamma, scale, shift, dgamma, dbeta, d
     st = stream(y.device)
     L = ext.lib()
     dt = dt_of(y)
-    check(L.pda_bn_bwd_reduce(C.byref(a), G, dt, st), "bn_bwd_reduce")
+    _bn_check(L.pda_bn_bwd_reduce(C.byref(a), G, dt, st), "bn_bwd_reduce", y)
     _bn_bwd_tail(ws, part, G, nq, mode, a, y, mean, invstd, gamma, dgamma, dbeta, dy_out,
                  y2, mean2, invstd2, gamma2, dgamma2, dbeta2, dy2_out, dz_buf, gscale, accumulate)
 
@@ -1054,6 +1075,7 @@ def bn_bwd_finish(ws: "Workspace", part, G: int, nq: int, y, mean, invstd, gamma
     SyncBatchNorm): the apply coefficients are written there and the apply pass of every branch
     whose output is None is skipped -- its consumer forms dy itself (:func:`conv_wgrad` ``bna``,
     :func:`conv_dgrad_bnf`)."""
+    _bn_shape("bn_bwd_finish", y)
     N, H, W, C_ = y.shape
     mode = 2 if nq == 3 else 1   # dz is materialised in both cases
     a = BwdArgs(None, None, None, 0, ptr(y), None, None, ptr(y2), None, None, mode, None, ptr(part),
@@ -1077,17 +1099,21 @@ def bn_bwd_finish(ws: "Workspace", part, G: int, nq: int, y, mean, invstd, gamma
         L, st, dt = ext.lib(), stream(y.device), dt_of(y)
         check(L.pda_bn_bwd_stats(ptr(part), G, nq, C_, S, ptr(slabs), ptr(cnt), C.byref(o),
                                  _stats_cg(C_), st), "bn_bwd_stats")
-        if mode == 2 and dy_out is not None and dy2_out is not None and _BWD_APPLY2 and \
-                L.pda_bn_bwd_apply2(ptr(dz), ptr(y), ptr(y2), ptr(k), ptr(dy_out), ptr(dy2_out),
-                                    N * H * W, C_, dt, st) == 0:
-            return   # both branches in one pass over dz
+        if mode == 2 and dy_out is not None and dy2_out is not None and _BWD_APPLY2:
+            rc = L.pda_bn_bwd_apply2(ptr(dz), ptr(y), ptr(y2), ptr(k), ptr(dy_out), ptr(dy2_out),
+                                     N * H * W, C_, dt, st)
+            if rc == 0:
+                return   # both branches in one pass over dz
+            if rc != -1:   # -1: this dtype / grid takes the two passes below
+                _bn_check(rc, "bn_bwd_apply2", y)
         if dy_out is not None:
-            check(L.pda_bn_bwd_apply(C.byref(a), ptr(dz), ptr(y), ptr(k[0:C_]), ptr(k[C_:2 * C_]),
-                                     ptr(k[2 * C_:3 * C_]), ptr(dy_out), dt, st), "bn_bwd_apply")
+            _bn_check(L.pda_bn_bwd_apply(C.byref(a), ptr(dz), ptr(y), ptr(k[0:C_]),
+                                         ptr(k[C_:2 * C_]), ptr(k[2 * C_:3 * C_]), ptr(dy_out), dt,
+                                         st), "bn_bwd_apply", y)
         if mode == 2 and dy2_out is not None:
-            check(L.pda_bn_bwd_apply(C.byref(a), ptr(dz), ptr(y2), ptr(k[3 * C_:4 * C_]),
-                                     ptr(k[4 * C_:5 * C_]), ptr(k[5 * C_:6 * C_]), ptr(dy2_out), dt,
-                                     st), "bn_bwd_apply2")
+            _bn_check(L.pda_bn_bwd_apply(C.byref(a), ptr(dz), ptr(y2), ptr(k[3 * C_:4 * C_]),
+                                         ptr(k[4 * C_:5 * C_]), ptr(k[5 * C_:6 * C_]), ptr(dy2_out),
+                                         dt, st), "bn_bwd_apply2", y)
         return
     _bn_bwd_tail(ws, part, G, nq, mode, a, y, mean, invstd, gamma, dgamma, dbeta, dy_out,
                  y2, mean2, invstd2, gamma2, dgamma2, dbeta2, dy2_out, dz, gscale, accumulate)

@@ -473,7 +473,8 @@ def check_case_conditions(cid: str, dtype) -> None:
 
 # ------------------------------------------------------------------ guarded buffers
 BAND = 1024   # bytes, a multiple of 256: the view keeps the alignment the kernels assume
-_ES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2, torch.uint8: 1, torch.float64: 8}
+_ES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2, torch.uint8: 1, torch.float64: 8,
+       torch.int32: 4, torch.int64: 8}
 
 
 def guarded(shape, dtype, fill=None, device="cpu", band_byte: int = 0xA5):
