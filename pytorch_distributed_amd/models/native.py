@@ -32,7 +32,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -40,6 +40,8 @@ from torch import nn
 from ..ops import ext
 from ..ops import native_ops as K
 from ..ops.native_ops import ConvGeom, Workspace
+from .native_train import (NativeCrossEntropy, NativeSGD, NativeTrainer,  # noqa: F401 (re-exported)
+                           _XentFn, _XentSoftFn)
 from .resnet import Bottleneck, ResNet
 
 __all__ = ["NativeResNet", "NativeSGD", "NativeCrossEntropy", "NativeTrainer", "supports"]
@@ -82,8 +84,13 @@ class ConvBN:
     bn_off: int = 0
     buf_off: int = 0
     nbt_idx: int = 0
-    # per-step state (f32 [C] each): mean, invstd, scale, shift
+    # per-step state (one f32 [4, C] tensor): the rows are mean, invstd, scale, shift
     state: Optional[torch.Tensor] = None
+
+    mean = property(lambda self: self.state[0])
+    invstd = property(lambda self: self.state[1])
+    scale = property(lambda self: self.state[2])
+    shift = property(lambda self: self.state[3])
 
     @property
     def cout(self) -> int:
@@ -109,6 +116,31 @@ class Block:
     seg: Tuple[int, int] = (0, 0)     # flat param range of this block
 
 
+@dataclass
+class _BlockSaved:
+    """What one residual block's forward keeps for its backward."""
+    x: torch.Tensor                        # block input
+    ys: List[torch.Tensor]                 # pre-BN output of every main-path conv
+    acts: List[Optional[torch.Tensor]]     # input of every conv; None: formed by the conv's prologue
+    yd: Optional[torch.Tensor] = None      # pre-BN output of the shortcut conv
+    mask: Optional[torch.Tensor] = None    # ReLU bitmask of an identity tail
+    gram: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # (B, s) of _fold_gram
+
+
+@dataclass
+class _Saved:
+    """What a saving forward keeps for the backward (``NativeResNet._fwd_ctx``). The BatchNorm
+    state is not in here: the backward reads it from the units, see ``gen``."""
+    x0: torch.Tensor                       # s2d input
+    gen: int                               # NativeResNet._state_gen of this forward
+    y0: torch.Tensor                       # pre-BN stem output
+    arg: torch.Tensor                      # max-pool argmax bytes
+    blocks: List[_BlockSaved]
+    feat: Optional[torch.Tensor] = None    # pooled features and logits: set when the forward ends
+    logits: Optional[torch.Tensor] = None
+    stem_gram: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # (B, s) of _stem_gram
+
+
 class NativeResNet(nn.Module):
     def __init__(self, ref: ResNet, device=None, dtype: torch.dtype = torch.bfloat16,
                  image_size: int = 224) -> None:
@@ -129,7 +161,13 @@ class NativeResNet(nn.Module):
         self._allocate(ref)
         self._reducer = None
         self._grads_zero = True
-        self._fwd_ctx = None
+        self._fwd_ctx: Optional[_Saved] = None
+        self._state_gen = 0       # counts forwards: which one the units' BN state belongs to
+        self._bufsync = None      # (comm, handle) of a pending DDP buffer broadcast
+        # the fused loss (native_train._XentFn) computes d(loss)/d(logits) as the padded 16-bit
+        # tensor the backward consumes and leaves it here; _NativeNetFn.backward takes it instead
+        # of converting the f32 placeholder autograd hands it
+        self._pending_dlog16: Optional[torch.Tensor] = None
         self._anchor = torch.zeros((), device=device, requires_grad=True)
         # BN1/BN2 (+ReLU) applied inside the consumer conv's operand staging (fwd and wgrad):
         # "1" every consumer, "1x1" only 1x1 consumers (a 3x3 consumer gathers each element 9x per
@@ -212,6 +250,7 @@ class NativeResNet(nn.Module):
         self.fork_tracking = os.environ.get("PDA_FORK_TRACK", "1") != "0"
         self._trk_ev = None
         self._trk_on = False
+        self._trk_c0 = 0          # pda_track_count() when tracking was armed
         # diagnostics (tools/layer_times.py): called on the main stream as probe(phase, name) after
         # the stem and after each residual block, forward and backward
         self.probe: Optional[Callable[[str, str], None]] = None
@@ -493,7 +532,7 @@ class NativeResNet(nn.Module):
         comm.broadcast(self.flat_bufstore, 0)
 
     def _join_bufsync(self) -> None:
-        pend = getattr(self, "_bufsync", None)
+        pend = self._bufsync
         if pend is not None:
             self._bufsync = None
             pend[0].wait(pend[1])
@@ -578,11 +617,10 @@ class NativeResNet(nn.Module):
         Nb = x.shape[0]
         g = u.geom(Nb)
         y = self._empty(Nb, g.Ho, g.Wo, u.cout)
-        st = u.state
         if train:   # batch statistics + BN finalize inside the conv launch
             bn = K.BnStats(ws, self.gamma(u), self.beta(u), u.bn.eps,
                            u.bn.momentum if u.bn.momentum is not None else 0.1,
-                           st[0], st[1], st[2], st[3], self.rmean(u), self.rvar(u),
+                           u.mean, u.invstd, u.scale, u.shift, self.rmean(u), self.rvar(u),
                            self.flat_nbt[u.nbt_idx:u.nbt_idx + 1], update_running=True)
             K.conv_fwd(x, self.w16(u), g, y, pro=pro, bn=bn, before_finalize=before_finalize,
                        tail=tail)
@@ -591,13 +629,8 @@ class NativeResNet(nn.Module):
             if before_finalize is not None:
                 before_finalize()
             K.bn_eval_coeffs(self.gamma(u), self.beta(u), self.rmean(u), self.rvar(u), u.bn.eps,
-                             st[2], st[3])
+                             u.scale, u.shift)
         return y
-
-    def _coeffs(self, u: ConvBN, train: bool):
-        """(scale, shift) of unit ``u`` written by its finalize (train) / eval-coefficient kernel:
-        views of the shared per-unit state, valid until the next forward of the same unit."""
-        return u.state[2], u.state[3]
 
     def native_forward(self, x: torch.Tensor, train: bool, save: bool) -> torch.Tensor:
         self._track(train)
@@ -609,41 +642,31 @@ class NativeResNet(nn.Module):
     def _native_forward(self, x: torch.Tensor, train: bool, save: bool) -> torch.Tensor:
         x = self.prepare_input(x)
         Nb = x.shape[0]
-        # per-unit BN state (mean/invstd/scale/shift) is referenced, not copied, by the saved
-        # context; any later forward overwrites it, which the generation check in backward catches
-        self._state_gen = getattr(self, "_state_gen", 0) + 1
-        saved: Dict = {"x0": x, "gen": self._state_gen} if save else None
+        # every forward overwrites the units' BN state (mean/invstd/scale/shift), which the
+        # backward reads from the units: the generation check in backward catches a stale one
+        self._state_gen += 1
         # stem: conv -> bn -> relu -> maxpool (fused); a pending DDP buffer broadcast joins
         # before the stem's BN finalize (the first write of the running statistics)
         y0 = self._conv_bn(self.stem, x, train, before_finalize=self._join_bufsync)
         ph = self.pool_hw
         p = self._empty(Nb, ph, ph, self.stem.cout)
         arg = torch.empty(Nb, ph, ph, self.stem.cout, dtype=torch.uint8, device=self.device)
-        sc, sh = self._coeffs(self.stem, train)
-        K.stem_pool(y0, sc, sh, p, arg)
+        K.stem_pool(y0, self.stem.scale, self.stem.shift, p, arg)
         if self.probe is not None:
             self.probe("fwd", "stem")
-        gram_pending = False
-        if save:
-            saved["y0"], saved["arg"] = y0, arg
-            saved["stem_stats"] = self.stem.state
-            saved["blocks"] = []
-            if self._stem_split_ok(Nb, y0):
-                saved["stem_gram"] = self._stem_gram(x, y0)
-                gram_pending = True
+        saved = _Saved(x, self._state_gen, y0, arg, []) if save else None
+        gram_pending = save and self._stem_split_ok(Nb, y0)
+        if gram_pending:
+            saved.stem_gram = self._stem_gram(x, y0)
         h = p
         feat = None
         nblk = len(self.blocks)
         tail_in = None   # (y3, (sc, sh), TailIn): the previous tail, folded into this block's conv1
         for bi, b in enumerate(self.blocks):
             last = bi == nblk - 1
-            rec = {"x": h} if save else None
-            a = h
-            ys, acts = [], [h]
-            pro = None
-            yd = None
-            if tail_in is not None:
-                a, pro = tail_in[0], tail_in[1]
+            a, pro = (h, None) if tail_in is None else tail_in[:2]
+            ys, acts, yd = [], [h], None
+            rec = _BlockSaved(h, ys, acts) if save else None
             # (SyncBatchNorm: the shortcut BN's all-reduce must not run on a second stream beside
             # the main chain's -- two streams on one communicator can order its collectives
             # differently on different ranks and deadlock -- so the shortcut stays on the chain)
@@ -667,13 +690,11 @@ class NativeResNet(nn.Module):
                 if j == 0 and ds_late:
                     yd = fork_ds()
                 ys.append(y)
-                if save:
-                    rec[f"s{j}"] = u.state
                 if j < len(b.units) - 1:
-                    sc, sh = self._coeffs(u, train)
+                    sc, sh = u.scale, u.shift
                     if gram_side and j == len(b.units) - 2:
                         gB, gs, forked = self._fold_gram(b.units[-1], y, sc, sh)
-                        rec["gram"] = (gB, gs)
+                        rec.gram = (gB, gs)
                         gram_pending = gram_pending or forked
                     if self._fuse_into(b.units[j + 1]):
                         # the next conv applies BN+ReLU while staging its tiles
@@ -688,10 +709,8 @@ class NativeResNet(nn.Module):
                     cur.wait_stream(self._side)
                 else:
                     yd = self._conv_bn(b.ds, h, train)
-                if save:
-                    rec["sd"] = b.ds.state
             ul = b.units[-1]
-            sc, sh = self._coeffs(ul, train)
+            sc, sh = ul.scale, ul.shift
             tail_in = None
             nb = self.blocks[bi + 1] if not last else None
             # the tail's BN apply folds into the next block's conv1 (FWD_TAIL; a downsampling next
@@ -703,36 +722,29 @@ class NativeResNet(nn.Module):
             fuse = (nb is not None and self.tail_fuse and (nb.ds is None or self.tail_fuse_ds)
                     and nb.units[0].cout <= 128
                     and K.tail_fuse_ok(nb.units[0].geom(Nb), self.dtype))
+            short = (dict(res=h) if yd is None
+                     else dict(y2=yd, scale2=b.ds.scale, shift2=b.ds.shift))
             if last:
                 feat = self._empty(Nb, ul.cout)
-                if yd is not None:
-                    K.tail_pool(ys[-1], sc, sh, feat, y2=yd, scale2=b.ds.state[2], shift2=b.ds.state[3])
-                else:
-                    K.tail_pool(ys[-1], sc, sh, feat, res=h)
+                K.tail_pool(ys[-1], sc, sh, feat, **short)
                 out = None
             else:
                 out = self._empty(*ys[-1].shape)
-                if yd is not None:
-                    if fuse:
-                        tail_in = (ys[-1], (sc, sh), K.TailIn(yd, out, sc2=b.ds.state[2],
-                                                              sh2=b.ds.state[3]))
-                    else:
-                        K.bn_apply(ys[-1], sc, sh, out, y2=yd, scale2=b.ds.state[2],
-                                   shift2=b.ds.state[3])
+                # identity tail: keep its ReLU bitmask (1/16 of the tensor) so the backward
+                # rebuilds the mask without re-reading the residual
+                mask = (torch.empty(out.numel() // 8, dtype=torch.uint8, device=self.device)
+                        if yd is None and save and self.tail_mask else None)
+                if not fuse:
+                    K.bn_apply(ys[-1], sc, sh, out, mask=mask, **short)
+                elif yd is None:
+                    tail_in = (ys[-1], (sc, sh), K.TailIn(h, out, mask=mask))
                 else:
-                    # identity tail: keep its ReLU bitmask (1/16 of the tensor) so the backward
-                    # rebuilds the mask without re-reading the residual
-                    mask = (torch.empty(out.numel() // 8, dtype=torch.uint8, device=self.device)
-                            if save and self.tail_mask else None)
-                    if fuse:
-                        tail_in = (ys[-1], (sc, sh), K.TailIn(h, out, mask=mask))
-                    else:
-                        K.bn_apply(ys[-1], sc, sh, out, res=h, mask=mask)
-                    if save:
-                        rec["mask"] = mask
+                    tail_in = (ys[-1], (sc, sh), K.TailIn(yd, out, sc2=b.ds.scale, sh2=b.ds.shift))
+                if save:
+                    rec.mask = mask
             if save:
-                rec["ys"], rec["acts"], rec["yd"] = ys, acts, yd
-                saved["blocks"].append(rec)
+                rec.yd = yd
+                saved.blocks.append(rec)
             h = out
             if self.probe is not None:
                 self.probe("fwd", b.name)
@@ -747,8 +759,7 @@ class NativeResNet(nn.Module):
         K.conv_fwd(feat, self.fc_w16, g, logits, tile=self._fc_tile(),
                    bias=self.flat_params[self.fc_b_off:self.fc_b_off + self.num_classes])
         if save:
-            saved["feat"] = feat
-            saved["logits"] = logits
+            saved.feat, saved.logits = feat, logits
         self._fwd_ctx = saved
         return logits
 
@@ -762,7 +773,7 @@ class NativeResNet(nn.Module):
                 self._trk_on = False
             return
         if (not self.fork_tracking or self._side is None or self.defer_side
-                or getattr(self.ws, "sync_comm", None) is not None
+                or self.ws.sync_comm is not None
                 or torch.cuda.is_current_stream_capturing()
                 or not ext.has("pda_track")):
             return
@@ -862,7 +873,9 @@ class NativeResNet(nn.Module):
         sv = self._fwd_ctx
         if sv is None:
             raise RuntimeError("native backward without a saved forward")
-        if sv["gen"] != self._state_gen:
+        # (this check is what lets the backward read mean / invstd / scale / shift from the units
+        # instead of from saved copies: they still hold this forward's values)
+        if sv.gen != self._state_gen:
             raise RuntimeError("another forward ran between this forward and its backward; the native "
                                "engine keeps one step of saved state (no retain_graph / interleaving)")
         acc = not self._grads_zero
@@ -883,9 +896,9 @@ class NativeResNet(nn.Module):
         def fc_wgrad(w):
             K.col_sum(dlog16, self.num_classes,
                       self.flat_grad[self.fc_b_off:self.fc_b_off + self.num_classes], accumulate=acc)
-            K.conv_wgrad(dlog16, sv["feat"], gfc, self.fc_wgrad_full, w, accumulate=acc,
+            K.conv_wgrad(dlog16, sv.feat, gfc, self.fc_wgrad_full, w, accumulate=acc,
                           wscale=self.wgrad_scale)
-        self._wgrad(fc_wgrad, dlog16, sv["feat"])
+        self._wgrad(fc_wgrad, dlog16, sv.feat)
         dfeat = self._empty(Nb, 1, 1, self.feat_dim)
         fc_w_ohwi = self.fc_w16.view(self.fc_rows, 1, 1, self.feat_dim)
         K.conv_dgrad(dlog16.view(Nb, 1, 1, self.fc_rows), fc_w_ohwi, gfc, dfeat, tile=self._fc_tile())
@@ -893,15 +906,12 @@ class NativeResNet(nn.Module):
             self._grads_ready(red, self.block_bounds[0])
         # ---- last block's tail: standalone reduction of the pooled gradient
         nblk = len(self.blocks)
-        b = self.blocks[-1]
-        rec = sv["blocks"][-1]
-        tail = self._tail_standalone(b, rec, dfeat.view(Nb, self.feat_dim), acc)
+        tail = self._tail_standalone(self.blocks[-1], sv.blocks[-1], dfeat.view(Nb, self.feat_dim))
         shortcut_g = None
         for bi in range(nblk - 1, -1, -1):
             b = self.blocks[bi]
-            rec = sv["blocks"][bi]
-            prev = (self.blocks[bi - 1], sv["blocks"][bi - 1]) if bi > 0 else None
-            dx_main, shortcut_g, tail = self._block_backward(b, rec, tail, prev, acc)
+            prev = (self.blocks[bi - 1], sv.blocks[bi - 1]) if bi > 0 else None
+            dx_main, shortcut_g, tail = self._block_backward(b, sv.blocks[bi], tail, prev, acc)
             if not self.defer_side and (self._wbatch_mode == "block" or b.ds is not None):
                 self._flush_wgrad()
             if bi == 0 or self.blocks[bi - 1].name[:6] != b.name[:6]:
@@ -913,61 +923,52 @@ class NativeResNet(nn.Module):
             if self.probe is not None:
                 self.probe("bwd", b.name)
         # ---- stem: maxpool backward of (main + shortcut) gradients, BN backward, wgrad
-        x0, y0, arg = sv["x0"], sv["y0"], sv["arg"]
-        st0 = sv["stem_stats"]
+        x0, y0, arg = sv.x0, sv.y0, sv.arg
         u = self.stem
         g0 = u.geom(Nb)
-        sync = getattr(ws, "sync_comm", None)
         # the stem's BN-backward output feeds only its weight gradient: with the fused stem
         # backward, the wgrad forms dy0 = k1*dz0 + k2*y0 + k3 while staging (no apply pass, no
         # dy0 write + re-read: 2 x 642 MB at batch 400)
-        bna = (self.fused_stem_bwd and self.stem_bna and (sync is None or sync.world_size == 1)
+        bna = (self.fused_stem_bwd and self.stem_bna and ws.local_stats
                and K.wgrad_bna_ok(g0, Nb, y0.dtype))
+        dz0 = dy0 = k0 = None
         if self.fused_stem_bwd:   # maxpool gather + ReLU mask + BN partials in one pass
             dz0 = self._empty(*y0.shape)
-            part, G, nq = K.stem_bwd_reduce(ws, dx_main, arg, y0, st0[2], st0[3], dz0,
+            part, G, nq = K.stem_bwd_reduce(ws, dx_main, arg, y0, u.scale, u.shift, dz0,
                                             dout2=shortcut_g)
             if bna:
                 k0 = self._stem_k
-                K.bn_bwd_finish(ws, part, G, nq, y0, st0[0], st0[1], self.gamma(u), self.dgamma(u),
-                                self.dbeta(u), dz0, None, accumulate=acc, k_out=k0)
             else:
                 dy0 = self._empty(*y0.shape)
-                K.bn_bwd_finish(ws, part, G, nq, y0, st0[0], st0[1], self.gamma(u), self.dgamma(u),
-                                self.dbeta(u), dz0, dy0, accumulate=acc)
+            K.bn_bwd_finish(ws, part, G, nq, y0, u.mean, u.invstd, self.gamma(u), self.dgamma(u),
+                            self.dbeta(u), dz0, dy0, accumulate=acc, k_out=k0)
         else:
             dy0 = self._empty(*y0.shape)
             dA0 = self._empty(*y0.shape)
             K.maxpool_bwd(dx_main, arg, dA0, dout2=shortcut_g)
-            K.bn_bwd(ws, y0, st0[0], st0[1], self.gamma(u), st0[2], st0[3], self.dgamma(u),
+            K.bn_bwd(ws, y0, u.mean, u.invstd, self.gamma(u), u.scale, u.shift, self.dgamma(u),
                      self.dbeta(u), dy0, g1=dA0, accumulate=acc)
-        if bna:
-            sg = sv.get("stem_gram")
+        sg = sv.stem_gram if bna else None
 
-            def stem_wgrad(w):
-                # (stem_s2d_grad reads the reduced gradient at once: its reduce runs unbatched)
-                rb, w.reduce_batch = w.reduce_batch, None
-                if sg is not None:   # decomposed: plain dz^T X, combined with k in the reduce
-                    K.conv_wgrad(dz0, x0, g0, self.stem_wgrad, w, combine=(k0, sg[0], sg[1]),
-                                 wscale=self.wgrad_scale)
-                else:
-                    K.conv_wgrad(dz0, x0, g0, self.stem_wgrad, w, bna=(y0, k0),
-                                 wscale=self.wgrad_scale)
-                w.reduce_batch = rb
-                K.stem_s2d_grad(self.stem_wgrad, self.wgrad_view(u), accumulate=acc)
-            if self._side is not None and not self.defer_side:
-                # the main stream is idle after the stem's BN backward while the second stream still
-                # drains layer1's weight gradients: the stem's runs beside them instead of after
-                stem_wgrad(ws)
+        def stem_wgrad(w):
+            # (stem_s2d_grad reads the reduced gradient at once: its reduce runs unbatched)
+            rb, w.reduce_batch = w.reduce_batch, None
+            if sg is not None:   # decomposed: plain dz^T X, combined with k in the reduce
+                K.conv_wgrad(dz0, x0, g0, self.stem_wgrad, w, combine=(k0, sg[0], sg[1]),
+                             wscale=self.wgrad_scale)
+            elif bna:            # dy0 = k1*dz0 + k2*y0 + k3 formed while staging
+                K.conv_wgrad(dz0, x0, g0, self.stem_wgrad, w, bna=(y0, k0),
+                             wscale=self.wgrad_scale)
             else:
-                self._wgrad(stem_wgrad, dz0, y0, x0, k0, split=False)   # (the last: no main work follows)
-        else:
-            def stem_wgrad(w):
-                rb, w.reduce_batch = w.reduce_batch, None
                 K.conv_wgrad(dy0, x0, g0, self.stem_wgrad, w, wscale=self.wgrad_scale)
-                w.reduce_batch = rb
-                K.stem_s2d_grad(self.stem_wgrad, self.wgrad_view(u), accumulate=acc)
-            self._wgrad(stem_wgrad, dy0, x0, split=False)
+            w.reduce_batch = rb
+            K.stem_s2d_grad(self.stem_wgrad, self.wgrad_view(u), accumulate=acc)
+        if bna and self._side is not None and not self.defer_side:
+            # the main stream is idle after the stem's BN backward while the second stream still
+            # drains layer1's weight gradients: the stem's runs beside them instead of after
+            stem_wgrad(ws)
+        else:   # (the last weight gradient: no main work follows)
+            self._wgrad(stem_wgrad, *((dz0, y0, x0, k0) if bna else (dy0, x0)), split=False)
         if not self.defer_side:
             self._flush_wgrad()
             self._flush_reduces()
@@ -981,35 +982,22 @@ class NativeResNet(nn.Module):
         self._grads_zero = False
         self._fwd_ctx = None
 
-    def _tail_args(self, b: Block, rec, use_mask: bool = False):
+    def _tail_args(self, b: Block, rec: _BlockSaved, use_mask: bool = False):
         """Tensors describing a = relu(bn3(y3) + shortcut) of block b for the BN-backward."""
         ul = b.units[-1]
-        sl = rec[f"s{len(b.units) - 1}"]
-        d = dict(y=rec["ys"][-1], scale=sl[2], shift=sl[3])
+        d = dict(y=rec.ys[-1], scale=ul.scale, shift=ul.shift)
         if b.ds is not None:
-            sd = rec["sd"]
-            d.update(y2=rec["yd"], scale2=sd[2], shift2=sd[3])
-        elif use_mask and rec.get("mask") is not None:
-            d.update(mask=rec["mask"])
+            d.update(y2=rec.yd, scale2=b.ds.scale, shift2=b.ds.shift)
+        elif use_mask and rec.mask is not None:
+            d.update(mask=rec.mask)
         else:
-            d.update(res=rec["x"])
+            d.update(res=rec.x)
         return d
 
-    def _tail_standalone(self, b: Block, rec, gp, acc):
+    def _tail_standalone(self, b: Block, rec: _BlockSaved, gp):
         """Tail reduction from the pooled head gradient (no producing dgrad to fuse into)."""
-        ys = rec["ys"]
-        dz = self._empty(*ys[-1].shape)
-        ta = self._tail_args(b, rec)
-        N, H, W, C_ = ys[-1].shape
-        G = K._reduce_blocks(N * H * W, C_)
-        nq = 3 if b.ds is not None else 2
-        part = self.ws.get("bn_part", G * nq * C_)
-        a = ext.BwdArgs(None, None, K.ptr(gp), H * W, K.ptr(ta["y"]), K.ptr(ta["scale"]),
-                        K.ptr(ta["shift"]), K.ptr(ta.get("y2", ta.get("res"))), K.ptr(ta.get("scale2")),
-                        K.ptr(ta.get("shift2")), 2 if b.ds is not None else 1, K.ptr(dz), K.ptr(part), nq,
-                        N * H * W, C_)
-        K.check(ext.lib().pda_bn_bwd_reduce(ext.C.byref(a), G, ext.dt_of(dz), ext.stream(dz.device)),
-                "bn_bwd_reduce")
+        dz = self._empty(*rec.ys[-1].shape)
+        part, G, nq = K.bn_bwd_reduce_pooled(self.ws, gp, dz, **self._tail_args(b, rec))
         return dz, part, G, nq
 
     def _tail_fold_ok(self, b: Block, Nb: int) -> bool:
@@ -1018,13 +1006,11 @@ class NativeResNet(nn.Module):
         statistics (SyncBatchNorm keeps the reduce / all-reduce / finalize path) and a weight-gradient
         plan the in-kernel BN operand (WGRAD_BNA) is built for."""
         ul = b.units[-1]
-        if not self.bn_fold or self.f32 or ul.conv.kernel_size != (1, 1):
+        if (not self.bn_fold or self.f32 or ul.conv.kernel_size != (1, 1)
+                or not self.ws.local_stats):
             return False
         if self.bn_fold_stages is not None and not (
                 b.name.startswith("layer") and int(b.name[5]) in self.bn_fold_stages):
-            return False
-        sync = getattr(self.ws, "sync_comm", None)
-        if sync is not None and sync.world_size > 1:
             return False
         g = ul.geom(Nb)
         return K.bnf_ok(g, self.dtype) and K.wgrad_bna_ok(g, Nb, self.dtype)
@@ -1039,9 +1025,8 @@ class NativeResNet(nn.Module):
     def _stem_split_ok(self, Nb: int, y0: torch.Tensor) -> bool:
         """Whether this training forward precomputes the stem weight gradient's y / colsum terms
         (``stem_split``): eager, a second stream, the fused WGRAD_BNA conditions."""
-        sync = getattr(self.ws, "sync_comm", None)
         return (self.stem_split and self._side is not None and not self.defer_side
-                and self.fused_stem_bwd and self.stem_bna and (sync is None or sync.world_size == 1)
+                and self.fused_stem_bwd and self.stem_bna and self.ws.local_stats
                 and y0.dtype in (torch.bfloat16, torch.float16)
                 and K.wgrad_bna_ok(self.stem.geom(Nb), Nb, y0.dtype))
 
@@ -1084,7 +1069,7 @@ class NativeResNet(nn.Module):
             K.fold_bgemm(self.w16(ul), gram[:C_], B)
         return B, gram[C_], True
 
-    def _block_backward(self, b: Block, rec, tail, prev, acc):
+    def _block_backward(self, b: Block, rec: _BlockSaved, tail, prev, acc):
         """Returns (dx_main, shortcut_grad, prev_tail) -- the last is the fused reduction of the
         previous block's tail, or None for the first block.
 
@@ -1095,26 +1080,24 @@ class NativeResNet(nn.Module):
         own forward; csrc/conv_gemm.hip DGRAD_BNF, bn_fold_kernel) -- the apply pass (read dz and
         y3, write dy3: three passes over the block's widest tensor) is gone from the chain."""
         ws = self.ws
-        x = rec["x"]
-        ys, acts, yd = rec["ys"], rec["acts"], rec["yd"]
+        x, ys, acts, yd = rec.x, rec.ys, rec.acts, rec.yd
         Nb = x.shape[0]
         n = len(b.units)
         ul = b.units[-1]
-        sl = rec[f"s{n - 1}"]
         dz, part, G, nq = tail
         fold = self._tail_fold_ok(b, Nb)
         kt = (torch.empty((nq - 1) * 3 * ul.cout, dtype=torch.float32, device=self.device)
               if fold else None)
         dy = None if fold else self._empty(*ys[-1].shape)
         sc_ev = None
+        dyd = self._empty(*yd.shape) if b.ds is not None else None
+        short = {} if b.ds is None else dict(
+            y2=yd, mean2=b.ds.mean, invstd2=b.ds.invstd, gamma2=self.gamma(b.ds),
+            dgamma2=self.dgamma(b.ds), dbeta2=self.dbeta(b.ds), dy2_out=dyd)
+        K.bn_bwd_finish(ws, part, G, nq, ys[-1], ul.mean, ul.invstd, self.gamma(ul), self.dgamma(ul),
+                        self.dbeta(ul), dz, dy, accumulate=acc, k_out=kt, **short)
         if b.ds is not None:
-            sd = rec["sd"]
             g = b.ds.geom(Nb)
-            dyd = self._empty(*yd.shape)
-            K.bn_bwd_finish(ws, part, G, nq, ys[-1], sl[0], sl[1], self.gamma(ul), self.dgamma(ul),
-                            self.dbeta(ul), dz, dy, y2=yd, mean2=sd[0], invstd2=sd[1],
-                            gamma2=self.gamma(b.ds), dgamma2=self.dgamma(b.ds), dbeta2=self.dbeta(b.ds),
-                            dy2_out=dyd, accumulate=acc, k_out=kt)
             # shortcut branch first: its dX is the second gradient source of the previous tail.
             # On the second stream its dgrad overlaps the conv3/conv2 chain; an event marks it for
             # the conv1 dgrad epilogue (or the stem) that consumes it
@@ -1136,11 +1119,8 @@ class NativeResNet(nn.Module):
                                                                     wscale=self.wgrad_scale),
                         dyd, x, split=fold)   # (fold: bn_fold launches before conv3's wgrad)
         else:
-            K.bn_bwd_finish(ws, part, G, nq, ys[-1], sl[0], sl[1], self.gamma(ul), self.dgamma(ul),
-                            self.dbeta(ul), dz, dy, accumulate=acc, k_out=kt)
             shortcut_g = dz
-        dx_main = None
-        prev_tail = None
+        dx_main = prev_tail = None
         cur = torch.cuda.current_stream(self.device)
         for j in range(n - 1, -1, -1):
             u = b.units[j]
@@ -1148,9 +1128,8 @@ class NativeResNet(nn.Module):
             g = u.geom(Nb)
             pro = None
             if a_in is None:   # fused prologue: recompute relu(bn(y_{j-1})) while staging B
-                sp_ = rec[f"s{j - 1}"]
                 a_in = ys[j - 1]
-                pro = (sp_[2], sp_[3])
+                pro = (b.units[j - 1].scale, b.units[j - 1].shift)
             bnf = None
             if fold and j == n - 1:
                 # tail fold: (dz, k) stand for dy3 in both of conv3's gradients
@@ -1160,21 +1139,16 @@ class NativeResNet(nn.Module):
                 fb = torch.empty(cin, dtype=torch.float32, device=self.device)
                 K.bn_fold(self.w16(u), k3, wf, fb, ws)
                 bnf = (wf, fb)
-                if "gram" in rec:   # decomposed form: plain dz^T a2, combined in the split-K reduce
-                    gB, gs = rec["gram"]
-                    self._wgrad(lambda w, u=u, g=g, a=a_in, pro=pro, k3=k3, gB=gB, gs=gs:
-                                K.conv_wgrad(dz, a, g, self.wgrad_view(u), w, accumulate=acc, pro=pro,
-                                             combine=(k3, gB, gs), wscale=self.wgrad_scale),
-                                dz, a_in, kt, gB, gs)
-                else:
-                    self._wgrad(lambda w, u=u, g=g, a=a_in, pro=pro, y3=ys[-1], k3=k3:
-                                K.conv_wgrad(dz, a, g, self.wgrad_view(u), w, accumulate=acc, pro=pro,
-                                             bna=(y3, k3), wscale=self.wgrad_scale),
-                                dz, a_in, ys[-1], kt)
+                if rec.gram is not None:   # decomposed: plain dz^T a2, combined in the reduce
+                    form, keep = dict(combine=(k3, *rec.gram)), (dz, a_in, kt, *rec.gram)
+                else:                      # dy3 formed from (dz, y3, k3) while staging
+                    form, keep = dict(bna=(ys[-1], k3)), (dz, a_in, ys[-1], kt)
+                src = dz
             else:
-                self._wgrad(lambda w, u=u, g=g, dy=dy, a=a_in, pro=pro:
-                            K.conv_wgrad(dy, a, g, self.wgrad_view(u), w, accumulate=acc, pro=pro,
-                                         wscale=self.wgrad_scale), dy, a_in)
+                src, form, keep = dy, {}, (dy, a_in)
+            self._wgrad(lambda w, u=u, g=g, src=src, a=a_in, pro=pro, form=form:
+                        K.conv_wgrad(src, a, g, self.wgrad_view(u), w, accumulate=acc, pro=pro,
+                                     wscale=self.wgrad_scale, **form), *keep)
 
             def dgrad(out, epi=None, u=u, g=g, dy=dy, bnf=bnf, a_in=a_in, pro=pro):
                 if bnf is not None:
@@ -1184,13 +1158,12 @@ class NativeResNet(nn.Module):
             out = self._empty(*a_in.shape)
             if j > 0:
                 up = b.units[j - 1]
-                sp = rec[f"s{j - 1}"]
                 Gp = K.dgrad_slabs(g, Nb, dtype=ys[-1].dtype)
                 # the dgrad's epilogue produces dz and the BN-backward partials of bn_{j-1}
-                epi, part_p, nq_p = K.bn_epilogue(ws, Gp, ys[j - 1], sp[2], sp[3])
+                epi, part_p, nq_p = K.bn_epilogue(ws, Gp, ys[j - 1], up.scale, up.shift)
                 dgrad(out, epi)                                      # out = dz of bn_{j-1}
                 dyp = self._empty(*ys[j - 1].shape)
-                K.bn_bwd_finish(ws, part_p, Gp, nq_p, ys[j - 1], sp[0], sp[1], self.gamma(up),
+                K.bn_bwd_finish(ws, part_p, Gp, nq_p, ys[j - 1], up.mean, up.invstd, self.gamma(up),
                                 self.dgamma(up), self.dbeta(up), out, dyp, accumulate=acc)
                 dy = dyp
             elif prev is not None:
@@ -1245,339 +1218,9 @@ class _NativeNetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         m: NativeResNet = ctx.model
-        pending = getattr(m, "_pending_dlog16", None)
-        if pending is not None:
-            dlog16 = pending
-            m._pending_dlog16 = None
-        else:  # generic criterion: convert f32 dlogits to the padded 16-bit buffer
+        dlog16, m._pending_dlog16 = m._pending_dlog16, None
+        if dlog16 is None:  # generic criterion: convert f32 dlogits to the padded 16-bit buffer
             dlog16 = torch.zeros(ctx.B, m.fc_rows, dtype=m.dtype, device=m.device)
             dlog16[:, :m.num_classes].copy_(dlogits)
         m.native_backward(dlog16)
         return None, None, None   # the anchor only routes autograd here: no gradient, no fill
-
-
-class _XentFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, model: NativeResNet):
-        B = logits.shape[0]
-        loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        K.xent(logits, labels, loss_rows, loss)
-        ctx.save_for_backward(logits, labels)
-        ctx.model = model
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels = ctx.saved_tensors
-        m: NativeResNet = ctx.model
-        B = logits.shape[0]
-        dlog16 = torch.empty(B, m.fc_rows, dtype=m.dtype, device=logits.device)
-        gdev = g.reshape(1).to(torch.float32).contiguous()
-        K.xent(logits, labels, torch.empty(B, device=logits.device), None, dlog=dlog16,
-               gscale=1.0 / B, gdev=gdev)
-        m._pending_dlog16 = dlog16
-        # the dlogits handed to the network node are carried by dlog16; return a placeholder
-        return torch.empty_like(logits), None, None
-
-
-class _XentSoftFn(torch.autograd.Function):
-    """:class:`_XentFn` against the soft target of two labels per row (K.xent_soft)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, labels_b, lam, eps, model: NativeResNet):
-        B = logits.shape[0]
-        loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        K.xent_soft(logits, labels, loss_rows, loss, labels_b=labels_b, lam=lam, eps=eps)
-        ctx.save_for_backward(logits, labels, *(() if labels_b is None else (labels_b,)))
-        ctx.model, ctx.lam, ctx.eps = model, lam, eps
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, labels, *rest = ctx.saved_tensors
-        m: NativeResNet = ctx.model
-        B = logits.shape[0]
-        dlog16 = torch.empty(B, m.fc_rows, dtype=m.dtype, device=logits.device)
-        gdev = g.reshape(1).to(torch.float32).contiguous()
-        K.xent_soft(logits, labels, torch.empty(B, device=logits.device), None,
-                    labels_b=rest[0] if rest else None, lam=ctx.lam, eps=ctx.eps, dlog=dlog16,
-                    gscale=1.0 / B, gdev=gdev)
-        m._pending_dlog16 = dlog16
-        return torch.empty_like(logits), None, None, None, None, None
-
-
-class NativeCrossEntropy(nn.Module):
-    """CrossEntropyLoss (mean) fused with its gradient kernel for the native engine.
-    ``label_smoothing`` (eps) and a second label per row with its weight (``labels_b``, ``lam``:
-    mixup / CutMix) select the soft-target kernel; with neither, the hard-label kernel runs."""
-
-    soft_targets = True      # forward takes (logits, labels, labels_b, lam): trainer.build_criterion
-
-    def __init__(self, model: Optional[NativeResNet] = None, label_smoothing: float = 0.0) -> None:
-        super().__init__()
-        if not 0.0 <= label_smoothing < 1.0:
-            raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
-        self.model = model
-        self.label_smoothing = float(label_smoothing)
-
-    def forward(self, logits: torch.Tensor, labels: torch.Tensor,
-                labels_b: Optional[torch.Tensor] = None, lam: float = 1.0) -> torch.Tensor:
-        m = self.model
-        eps = self.label_smoothing
-        if m is None or not logits.is_cuda or logits.dtype != torch.float32:
-            x = logits.float()
-            if eps == 0.0 and labels_b is None:
-                return nn.functional.cross_entropy(x, labels)
-            from ..mix import soft_cross_entropy
-            return soft_cross_entropy(x, labels, labels_b, lam, eps)
-        if eps == 0.0 and labels_b is None:
-            if logits.requires_grad:
-                return _XentFn.apply(logits, labels, m)
-            B = logits.shape[0]
-            loss = torch.empty((), dtype=torch.float32, device=logits.device)
-            K.xent(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss)
-            return loss
-        lam = float(lam)
-        if logits.requires_grad:
-            return _XentSoftFn.apply(logits, labels, labels_b, lam, eps, m)
-        B = logits.shape[0]
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        K.xent_soft(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss,
-                    labels_b=labels_b, lam=lam, eps=eps)
-        return loss
-
-
-class NativeSGD(torch.optim.Optimizer):
-    """torch.optim.SGD semantics (momentum, dampening 0, weight decay on every parameter -- as the
-    reference, quirk Q12) executed as ONE fused kernel over the flat buffers, which also refreshes
-    the 16-bit weight shadow. ``state_dict()`` has torch SGD's format (per-parameter
-    ``momentum_buffer``), so checkpoints interchange with the reference's optimizer.
-
-    ``param_groups`` (torch-style group dicts: ``params`` plus any of ``lr``, ``momentum``,
-    ``weight_decay``, ``nesterov``, ``lars``, ``lars_eps``; the constructor arguments are the
-    defaults), ``nesterov=True`` or a trust coefficient ``lars > 0`` select the *segmented* step
-    (``self.segmented``): one ``sgd_seg`` launch (``csrc/optim.hip``) that reads each parameter
-    tensor's hyper-parameters from a device table, after a ``seg_norms`` launch when some group has a
-    trust coefficient. Parameters given to no group are frozen: their master weights, momentum and
-    shadow are never touched. The groups' hyper-parameters may change between steps (``StepLR``); the
-    table is re-uploaded when they do. Without these arguments the optimizer is the one-launch
-    ``sgd_flat`` step, unchanged."""
-
-    @staticmethod
-    def wants_segments(param_groups=None, nesterov=False, lars=0.0, **_kw) -> bool:
-        """Whether these constructor arguments select the segmented step."""
-        return param_groups is not None or bool(nesterov) or lars != 0
-
-    def __init__(self, model: NativeResNet, lr=0.1, momentum=0.9, weight_decay=1e-4,
-                 dampening=0.0, nesterov=False, lars=0.0, lars_eps=1e-8, param_groups=None) -> None:
-        self._sealed = False
-        self.segmented = self.wants_segments(param_groups, nesterov, lars)
-        if dampening != 0.0:
-            raise ValueError("NativeSGD implements dampening=0 (reference setting)")
-        defaults = dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay,
-                        nesterov=False, maximize=False, foreach=None, differentiable=False,
-                        fused=None)
-        if self.segmented:
-            from ..optim import normalize_param_groups
-            defaults.update(nesterov=bool(nesterov), lars=lars, lars_eps=lars_eps)
-            groups = normalize_param_groups(list(model.parameters()), param_groups, defaults)
-            if not any(g["params"] for g in groups):
-                raise ValueError("NativeSGD: the parameter groups hold no parameter")
-            super().__init__(groups, defaults)
-        else:
-            super().__init__(list(model.parameters()), defaults)
-        self._sealed = True
-        self.model = model
-        self.flat_mom = torch.zeros_like(model.flat_params)
-        self._initialized = False
-        # per-parameter momentum views (torch format in state_dict)
-        self._views = {}
-        fp = model.flat_params
-        base = fp.data_ptr()
-        segments = []
-        for g in self.param_groups:
-            for p in g["params"]:
-                off = (p.data_ptr() - base) // 4
-                segments.append((off, p.numel()))
-                v = self.flat_mom[off:off + p.numel()]
-                if p.dim() == 4:
-                    O, I, R, S_ = p.shape
-                    v = v.view(O, R, S_, I).permute(0, 3, 1, 2)
-                else:
-                    v = v.view(p.shape)
-                self._views[p] = v
-        if self.segmented:
-            # one segment per parameter tensor (the fc weight: its num_classes rows, not the padded
-            # ones), in group order; the device table is built once and re-uploaded on a change
-            self._uploaded = self._hyper_rows()
-            self._tables, _ = K.seg_tables(segments, self._uploaded, fp.device)
-
-    def add_param_group(self, param_group) -> None:
-        if getattr(self, "_sealed", False):
-            raise ValueError("NativeSGD: the groups are fixed at construction (the segment table is "
-                             "built once); pass param_groups to the constructor")
-        super().add_param_group(param_group)
-
-    def zero_grad(self, set_to_none: bool = True) -> None:
-        self.model.zero_grad_flat()
-
-    def _hyper_rows(self) -> list:
-        """One hyper-parameter row per segment, from the groups as they are now."""
-        from ..optim import GROUP_KEYS, check_hyper
-        rows = []
-        for i, g in enumerate(self.param_groups):
-            h = {k: g[k] for k in GROUP_KEYS}
-            check_hyper(h, f"NativeSGD: param_groups[{i}]: ")
-            rows += [h] * len(g["params"])
-        return rows
-
-    def _launch_segments(self, inv_scale=None, found_inf=None) -> None:
-        m = self.model
-        rows = self._hyper_rows()
-        if rows != self._uploaded:      # a scheduler (or the user) edited a group since the last step
-            self._tables.set_hyper(rows)
-            self._uploaded = rows
-        if self._tables.any_trust:
-            K.seg_norms(m.flat_params, m.flat_grad, self._tables)
-        K.sgd_seg(m.flat_params, m.flat_grad, self.flat_mom, None if m.f32 else m.flat_shadow,
-                  self._tables, self._initialized, inv_scale=inv_scale, found_inf=found_inf)
-
-    def _launch_range(self, lo: int, hi: int, inv_scale=None, found_inf=None) -> None:
-        g = self.param_groups[0]
-        m = self.model
-        K.sgd_flat(m.flat_params[lo:hi], m.flat_grad[lo:hi], self.flat_mom[lo:hi],
-                   None if m.f32 else m.flat_shadow[lo:hi], g["lr"], g["momentum"],
-                   g["weight_decay"], self._initialized, inv_scale=inv_scale, found_inf=found_inf)
-
-    def _launch(self, inv_scale=None, found_inf=None) -> None:
-        g = self.param_groups[0]
-        m = self.model
-        if m._grads_zero:
-            # zero_grad() and no backward since: torch 2.x's set_to_none leaves every .grad None,
-            # and SGD skips parameters without a gradient -- the flat gradient still holds the
-            # previous step's values (no memset), so applying it would be a stale update
-            return
-        if self.segmented:
-            self._launch_segments(inv_scale, found_inf)
-        else:
-            self._launch_range(0, m.numel, inv_scale, found_inf)
-        m._pack_stem()
-        # (an overflow-skipped first step leaves the momentum buffer unset on the device but the
-        # flag set: the next step then reads the zero-initialised buffer, m*0 + d == d)
-        self._initialized = True
-        for g in self.param_groups:
-            for p in g["params"]:
-                self.state[p]["momentum_buffer"] = self._views[p]
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        self._launch()
-        return loss
-
-    @torch.no_grad()
-    def step_amp(self, scale: torch.Tensor, found_inf: torch.Tensor, tracker=None,
-                 growth_factor: float = 2.0, backoff_factor: float = 0.5,
-                 growth_interval: int = 2000) -> None:
-        """AMP step, two launches and no host sync: ``amp_scan`` (non-finite check of the flat
-        gradient; its last workgroup publishes found_inf and 1/scale and, given ``tracker``, runs
-        the GradScaler scale update) then the fused SGD, which unscales by 1/scale and skips the
-        whole update when found_inf is set."""
-        if getattr(self, "_amp_ws", None) is None or self._amp_ws.device != scale.device:
-            self._amp_ws = torch.zeros(2, dtype=torch.int32, device=scale.device)
-            self._amp_inv = torch.ones(1, dtype=torch.float32, device=scale.device)
-        K.amp_scan(self.model.flat_grad, found_inf, self._amp_inv, scale, tracker, self._amp_ws,
-                   growth_factor, backoff_factor, growth_interval)
-        self._launch(inv_scale=self._amp_inv, found_inf=found_inf)
-
-    def state_dict(self):
-        sd = super().state_dict()
-        return sd
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        if self.segmented:
-            # a checkpoint of a plain torch.optim.SGD carries no lars / lars_eps: keep the defaults
-            for g in self.param_groups:
-                for k, v in self.defaults.items():
-                    g.setdefault(k, v)
-        with torch.no_grad():
-            any_buf = False
-            for g in self.param_groups:
-                for p in g["params"]:
-                    st = self.state.get(p, {})
-                    buf = st.get("momentum_buffer")
-                    if buf is not None:
-                        self._views[p].copy_(buf)
-                        st["momentum_buffer"] = self._views[p]
-                        any_buf = True
-            self._initialized = any_buf
-
-
-# ====================================================================== bench trainer
-class NativeTrainer:
-    engine = "native"
-
-    def __init__(self, arch, batch, dtype, device, world=1, rank=0, bucket_mb=32.0, image_size=224,
-                 graph: bool = False):
-        from .resnet import build_model
-        from ..data.synthetic import SyntheticImageNet
-        torch.manual_seed(0)
-        ref = build_model(arch)
-        self.model = NativeResNet(ref, device=device, dtype=dtype, image_size=image_size)
-        self.net = self.model
-        if world > 1:
-            from ..parallel.ddp import DistributedDataParallel
-            self.net = DistributedDataParallel(self.model, bucket_cap_mb=bucket_mb)
-        self.opt = self.model.make_optimizer(lr=0.1, momentum=0.9, weight_decay=1e-4)
-        self.crit = self.model.make_criterion()
-        self.ds = SyntheticImageNet("train", seed=0, image_size=image_size)
-        self.gen = self.model.input_generator(self.ds)
-        self.batch, self.world, self.rank, self.device = batch, world, rank, device
-        self.scaler = None
-        if dtype == torch.float16:
-            from ..amp import LossScaler
-            self.scaler = LossScaler()
-        self._loss = None
-        self.graphed = None
-        if graph:
-            from ..runtime.graphs import graphs_unsafe_warning, single_queue_graphs
-            if not single_queue_graphs():
-                graphs_unsafe_warning("NativeTrainer(graph=True)")
-                graph = False
-        if graph:
-            if world > 1:
-                raise ValueError("graph capture of the distributed step is not enabled (RCCL "
-                                 "collectives stay eager); use graph=False with world > 1")
-            from ..runtime.graphs import GraphedNativeStep
-            self.graphed = GraphedNativeStep(self.model, self.opt, self.gen, batch, self.scaler,
-                                             device)
-
-    def step(self, i: int) -> None:
-        if self.graphed is not None:
-            self.graphed.run((i * self.world + self.rank) * self.batch)
-            self._loss = self.graphed.loss
-            return
-        ids = torch.arange(self.batch, dtype=torch.int64) + (i * self.world + self.rank) * self.batch
-        x, y = self.gen(ids)
-        out = self.net(x)
-        loss = self.crit(out, y)
-        if self.scaler is not None:
-            self.scaler.scale(loss).backward()
-            self.scaler.step(self.opt)
-            self.scaler.update()
-        else:
-            loss.backward()
-            self.opt.step()
-        self.opt.zero_grad()
-        self._loss = loss.detach()
-
-    def last_loss(self):
-        return None if self._loss is None else float(self._loss.item())
-
-    def state_checksum(self) -> torch.Tensor:
-        """Bit-exact checksum of master weights + momentum (bench cross-rank consistency)."""
-        from ..bench_step import tensor_checksum
-        return tensor_checksum([self.model.flat_params, self.opt.flat_mom])

@@ -115,6 +115,11 @@ class Workspace:
         self.sync_comm = None
         self.reduce_batch: Optional[ReduceBatch] = None   # set: conv_wgrad queues its reduce
 
+    @property
+    def local_stats(self) -> bool:
+        """BatchNorm statistics are per rank: no SyncBatchNorm, or a communicator of one rank."""
+        return self.sync_comm is None or self.sync_comm.world_size == 1
+
     def get(self, name: str, numel: int, dtype=torch.float32) -> torch.Tensor:
         b = self._bufs.get(name)
         if b is None or b.numel() < numel or b.dtype != dtype:
@@ -238,6 +243,18 @@ def fwd_tile(g: ConvGeom, Nb: int, dtype: torch.dtype, pro: bool = False,
     return pick_tile(M, g.Cout, Kpad if Kpad is not None else g.R * g.S * g.Cin)
 
 
+def _launch_fwd(launch, what: str, T: int, rows: int, M: int, Cout: int, stats, bn, before_finalize):
+    """What the three forward launches share: the workspace's statistics buffer (T tiles of ``rows``
+    rows of M) when ``bn`` is given, ``launch(stats)`` -> rc, ``before_finalize``, the BN finalize."""
+    if bn is not None:
+        stats = bn.ws.get("fwd_stats", T * 3 * Cout)
+    check(launch(stats), what)
+    if before_finalize is not None:
+        before_finalize()
+    if bn is not None:
+        bn_finalize_partials(stats, T, Cout, rows, M, bn)
+
+
 def conv_fwd(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: torch.Tensor,
              stats: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
              relu: bool = False, tile: Optional[Tuple[int, int]] = None,
@@ -272,17 +289,12 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: torch.Tensor,
     pitch = out.stride(0) if out.dim() == 2 else g.Cout
     kdt = _kdt(x)
     kbm, kbn = _ktile(bm, bn_, kdt, pro is not None or g.Cin < 64)
-    T = math.ceil(M / tile_rows(kbm))
-    if bn is not None:
-        stats = bn.ws.get("fwd_stats", T * 3 * g.Cout)
-    rc = ext.lib().pda_conv_fwd(C.byref(d), ptr(x), ptr(w), Kpad, ptr(out), int(out_f32), pitch,
-                                ptr(bias), ptr(stats), int(relu), ptr(pro[0] if pro else None),
-                                ptr(pro[1] if pro else None), kdt, kbm, kbn, stream(x.device))
-    check(rc, "conv_fwd")
-    if before_finalize is not None:
-        before_finalize()
-    if bn is not None:
-        bn_finalize_partials(stats, T, g.Cout, tile_rows(kbm), M, bn)
+    _launch_fwd(lambda st: ext.lib().pda_conv_fwd(
+        C.byref(d), ptr(x), ptr(w), Kpad, ptr(out), int(out_f32), pitch, ptr(bias), ptr(st),
+        int(relu), ptr(pro[0] if pro else None), ptr(pro[1] if pro else None), kdt, kbm, kbn,
+        stream(x.device)),
+        "conv_fwd", math.ceil(M / tile_rows(kbm)), tile_rows(kbm), M, g.Cout, stats, bn,
+        before_finalize)
     return out
 
 
@@ -319,19 +331,13 @@ def _conv_fwd_tail(y3, w, g: ConvGeom, out, pro, tail: TailIn, stats, bn, before
     M = Nb * g.Ho * g.Wo
     Kpad = w.shape[-1] if w.dim() == 2 else w[0].numel()
     bm, bn_ = -128, (64 if g.Cout <= 64 else 128)
-    T = math.ceil(M / 128)
-    if bn is not None:
-        stats = bn.ws.get("fwd_stats", T * 3 * g.Cout)
     mode = 2 if tail.sc2 is not None else 1
     d = g.desc(Nb)
-    check(ext.lib().pda_conv_fwd_tail(C.byref(d), ptr(y3), ptr(w), Kpad, ptr(out), ptr(stats),
-                                      ptr(pro[0]), ptr(pro[1]), ptr(tail.res), ptr(tail.sc2),
-                                      ptr(tail.sh2), ptr(tail.out), ptr(tail.mask), mode,
-                                      _kdt(y3), bm, bn_, stream(y3.device)), "conv_fwd_tail")
-    if before_finalize is not None:
-        before_finalize()
-    if bn is not None:
-        bn_finalize_partials(stats, T, g.Cout, 128, M, bn)
+    _launch_fwd(lambda st: ext.lib().pda_conv_fwd_tail(
+        C.byref(d), ptr(y3), ptr(w), Kpad, ptr(out), ptr(st), ptr(pro[0]), ptr(pro[1]),
+        ptr(tail.res), ptr(tail.sc2), ptr(tail.sh2), ptr(tail.out), ptr(tail.mask), mode, _kdt(y3),
+        bm, bn_, stream(y3.device)),
+        "conv_fwd_tail", math.ceil(M / 128), 128, M, g.Cout, stats, bn, before_finalize)
     return out
 
 
@@ -361,17 +367,12 @@ def stem_fwd(x: torch.Tensor, w: torch.Tensor, g: ConvGeom, out: torch.Tensor,
     M = Nb * g.Ho * g.Wo
     rows = stem_stats_rows(g)
     T = M // rows
-    if bn is not None:
-        stats = bn.ws.get("fwd_stats", T * 3 * g.Cout)
-    if stats is not None and stats.numel() < T * 3 * g.Cout:
+    if bn is None and stats is not None and stats.numel() < T * 3 * g.Cout:
         raise ValueError(f"stem_fwd: stats needs {T * 3 * g.Cout} floats (one partial per output "
                          f"row, stem_stats_rows), got {stats.numel()}")
-    check(ext.lib().pda_stem_fwd(ptr(x), ptr(w), ptr(out), ptr(stats), Nb, g.H, g.W, _kdt(x),
-                                 _STEM_GRID, stream(x.device)), "stem_fwd")
-    if before_finalize is not None:
-        before_finalize()
-    if bn is not None:
-        bn_finalize_partials(stats, T, g.Cout, rows, M, bn)
+    _launch_fwd(lambda st: ext.lib().pda_stem_fwd(ptr(x), ptr(w), ptr(out), ptr(st), Nb, g.H, g.W,
+                                                  _kdt(x), _STEM_GRID, stream(x.device)),
+                "stem_fwd", T, rows, M, g.Cout, stats, bn, before_finalize)
     return out
 
 
@@ -400,9 +401,7 @@ def bn_finalize_partials(stats: torch.Tensor, T: int, C_: int, bm: int, M: int, 
     ws = bn.ws
     slabs = ws.get("bn_slabs", S * 2 * C_, torch.float64)
     cnt = ws.counters(G)
-    sync = getattr(ws, "sync_comm", None)
-    if sync is not None and sync.world_size == 1:
-        sync = None
+    sync = None if ws.local_stats else ws.sync_comm
     tot = ws.get("bn_tot", 2 * C_, torch.float64) if sync is not None else None
     o = ext.BnFwdOut(ptr(bn.gamma), ptr(bn.beta), bn.eps, bn.momentum, ptr(bn.mean),
                      ptr(bn.invstd), ptr(bn.scale), ptr(bn.shift), ptr(bn.rmean), ptr(bn.rvar),
@@ -931,12 +930,12 @@ def prereduce(part: torch.Tensor, G: int, QC: int, ws: Optional["Workspace"] = N
     return out, s
 
 
-def _sync_sums(part: torch.Tensor, G: int, QC: int, ws: Optional["Workspace"]):
+def _sync_sums(part: torch.Tensor, G: int, QC: int, ws: "Workspace"):
     """SyncBatchNorm: [G][QC] partials -> one [QC] row (own slab kernel, fixed order), summed over
     the ranks of ``ws.sync_comm`` (ordered on the current stream). Returns (part, G, world)."""
-    comm = getattr(ws, "sync_comm", None)
-    if comm is None or comm.world_size == 1:
+    if ws.local_stats:
         return part, G, 1
+    comm = ws.sync_comm
     tot = ws.get("bn_sync", QC)
     if ext.lib().pda_slab_reduce(ptr(part), G, QC, 1, ptr(tot), stream(part.device)) < 0:
         raise RuntimeError("slab_reduce launch failed")
@@ -1062,6 +1061,22 @@ def bn_bwd(ws: Workspace, y, mean, invstd, gamma, scale, shift, dgamma, dbeta, d
                  y2, mean2, invstd2, gamma2, dgamma2, dbeta2, dy2_out, dz_buf, gscale, accumulate)
 
 
+def bn_bwd_reduce_pooled(ws: "Workspace", gp, dz, y, scale, shift, res=None, y2=None, scale2=None,
+                         shift2=None):
+    """BN-backward reduction of the last tail a = relu(bn(y) [+res | +bn2(y2)]) from the pooled head
+    gradient ``gp`` [N][C] (each position's gradient is gp / HW: no producing dgrad to fuse into).
+    Writes the masked gradient ``dz``; returns (part, G, nq) for :func:`bn_bwd_finish`."""
+    N, H, W, C_ = y.shape
+    G = _reduce_blocks(N * H * W, C_)
+    nq = 3 if y2 is not None else 2
+    part = ws.get("bn_part", G * nq * C_)
+    a = BwdArgs(None, None, ptr(gp), H * W, ptr(y), ptr(scale), ptr(shift),
+                ptr(y2 if y2 is not None else res), ptr(scale2), ptr(shift2),
+                2 if y2 is not None else 1, ptr(dz), ptr(part), nq, N * H * W, C_)
+    check(ext.lib().pda_bn_bwd_reduce(C.byref(a), G, dt_of(dz), stream(dz.device)), "bn_bwd_reduce")
+    return part, G, nq
+
+
 def bn_bwd_finish(ws: "Workspace", part, G: int, nq: int, y, mean, invstd, gamma, dgamma, dbeta,
                   dz, dy_out, y2=None, mean2=None, invstd2=None, gamma2=None, dgamma2=None,
                   dbeta2=None, dy2_out=None, gscale: float = 1.0, accumulate: bool = False,
@@ -1080,11 +1095,9 @@ def bn_bwd_finish(ws: "Workspace", part, G: int, nq: int, y, mean, invstd, gamma
     mode = 2 if nq == 3 else 1   # dz is materialised in both cases
     a = BwdArgs(None, None, None, 0, ptr(y), None, None, ptr(y2), None, None, mode, None, ptr(part),
                 nq, N * H * W, C_)
-    sync = getattr(ws, "sync_comm", None)
-    if k_out is not None and ((sync is not None and sync.world_size > 1)
-                              or k_out.numel() < 3 * (nq - 1) * C_):
+    if k_out is not None and (not ws.local_stats or k_out.numel() < 3 * (nq - 1) * C_):
         raise ValueError("bn_bwd_finish: k_out needs the non-synchronised form and 3 x C per branch")
-    if sync is None or sync.world_size == 1:
+    if ws.local_stats:
         k = ws.get("bn_k", 6 * C_) if k_out is None else k_out
         S = _stats_slabs(G, C_)
         slabs = ws.get("bn_slabs", S * nq * C_, torch.float64)

@@ -143,6 +143,12 @@ class DataParallel(nn.Module):
         # caller
         self.replay_timeout_s = float(os.environ.get("PDA_DP_REPLAY_TIMEOUT_S", "120"))
         self._ev_bwd = self._ev_comm = None
+        # replica graphs (train_step_chunks): one _ReplicaGraph per module, for these input shapes
+        self._graphs: Optional[list] = None
+        self._graph_shapes: Optional[list] = None
+        self._segments_verified = False      # the first segmented replay compared the replicas
+        self._force_single_segment = False   # ... and they differed: one graph, one all-reduce
+        self._cstreams: Optional[list] = None   # a communication stream per device, on first use
 
     # ------------------------------------------------------------------ construction
     def _native_replica(self, dev: torch.device):
@@ -336,7 +342,7 @@ class DataParallel(nn.Module):
                 graph = False
         self._broadcast_state()
         B = sum(x.shape[0] for x in xs)
-        if getattr(self, "_graphs", None) is None or [x.shape for x in xs] != self._graph_shapes:
+        if self._graphs is None or [x.shape for x in xs] != self._graph_shapes:
             splits = self._segment_bounds()
             self._graphs = [_ReplicaGraph(m, x.shape, B, splits) for m, x in zip(self.all_modules, xs)]
             self._graph_shapes = [x.shape for x in xs]
@@ -345,10 +351,10 @@ class DataParallel(nn.Module):
         replay = graph and all(rg.graphs for rg in self._graphs)
         if replay and self.replicas:
             self._replay_overlapped(jobs, streams)
-            if len(jobs[0][0].graphs) > 1 and not getattr(self, "_segments_verified", False):
+            if len(jobs[0][0].graphs) > 1 and not self._segments_verified:
                 self._verify_segmented_reduce(optimizer)
                 loss = self._step_loss(xs, B)   # this step's graphs hold its losses
-                if getattr(self, "_force_single_segment", False):
+                if self._force_single_segment:
                     self._graphs = None         # re-captured without split points next step
                 return loss
         else:
@@ -410,13 +416,13 @@ class DataParallel(nn.Module):
         mode = os.environ.get("PDA_DP_SEGMENTS", "stage")
         if mode not in ("stage", "0"):
             raise ValueError(f"PDA_DP_SEGMENTS={mode!r}: expected stage or 0")
-        if (mode == "0" or getattr(self, "_force_single_segment", False) or not self.replicas
+        if (mode == "0" or self._force_single_segment or not self.replicas
                 or not hasattr(self.module, "stage_bounds")):
             return []
         return self.module.stage_bounds()
 
     def _comm_streams(self):
-        if getattr(self, "_cstreams", None) is None:
+        if self._cstreams is None:
             self._cstreams = [torch.cuda.Stream(torch.device("cuda", d)) for d in self.device_ids]
         return self._cstreams
 

@@ -282,7 +282,7 @@ def test_dataparallel_segment_bounds_and_step_busy(monkeypatch):
             return [100, 200, 300]
 
     dp = DataParallel.__new__(DataParallel)     # no devices here: only the policy's inputs
-    dp.__dict__.update(module=Fake(), replicas=[object()])
+    dp.__dict__.update(module=Fake(), replicas=[object()], _force_single_segment=False)
     monkeypatch.setenv("PDA_DP_SEGMENTS", "stage")
     assert dp._segment_bounds() == [100, 200, 300]
     monkeypatch.setenv("PDA_DP_SEGMENTS", "0")

@@ -48,9 +48,9 @@ def main():
     ln = nm.native_forward(x, train=True, save=True)
     sv = nm._fwd_ctx
     names = [b.name for b in nm.blocks]
-    print("stem y0 (pre-bn) vs torch conv1:", rel(sv["y0"].permute(0, 3, 1, 2), tm.conv1(x)))
+    print("stem y0 (pre-bn) vs torch conv1:", rel(sv.y0.permute(0, 3, 1, 2), tm.conv1(x)))
     for i, n in enumerate(names[:-1]):
-        nat = sv["blocks"][i + 1]["x"].permute(0, 3, 1, 2)
+        nat = sv.blocks[i + 1].x.permute(0, 3, 1, 2)
         print(f"{n:12s} native {rel(nat, fo[n]):.4f}   torch-bf16 {rel(bo[n], fo[n]):.4f}")
     print("logits      native", rel(ln, lt), " torch-bf16", rel(lb, lt))
 

@@ -26,7 +26,7 @@ def main() -> None:
     x, _ = gen(torch.arange(Nb))
     m.native_forward(x, train=True, save=True)
     sv = m._fwd_ctx
-    x0, y0, arg, st0 = sv["x0"], sv["y0"], sv["arg"], sv["stem_stats"]
+    x0, y0, arg = sv.x0, sv.y0, sv.arg
     u = m.stem
     g0 = u.geom(Nb)
     ws, ws_w = m.ws, m.ws_w
@@ -50,13 +50,13 @@ def main() -> None:
         return ts[len(ts) // 2]
 
     MB = 1e-6
-    red = lambda: K.stem_bwd_reduce(ws, dout, arg, y0, st0[2], st0[3], dz0, dout2=dout2)
+    red = lambda: K.stem_bwd_reduce(ws, dout, arg, y0, u.scale, u.shift, dz0, dout2=dout2)
     mb_red = (dout.numel() * 2 * 2 + arg.numel() + y0.numel() * 2 * 2) * MB
     t = timed(red)
     print(f"stem_bwd_reduce alone        {t:8.1f} us  {mb_red / t:5.2f} TB/s ({mb_red:.0f} MB)")
     part, G, nq = red()
     k0 = m._stem_k
-    K.bn_bwd_finish(ws, part, G, nq, y0, st0[0], st0[1], m.gamma(u), m.dgamma(u), m.dbeta(u),
+    K.bn_bwd_finish(ws, part, G, nq, y0, u.mean, u.invstd, m.gamma(u), m.dgamma(u), m.dbeta(u),
                     dz0, None, k_out=k0)
     mb_x = x0.numel() * 2 * MB
     if K.wgrad_bna_ok(g0, Nb, y0.dtype):
