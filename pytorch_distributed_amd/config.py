@@ -59,6 +59,7 @@ class RunConfig:
     ema: float = 0.0                 # weight-EMA decay in (0, 1) (0 = off)
     ema_every: int = 1               # EMA update interval in optimizer steps
     ema_warmup: bool = True          # EMA decay min(decay, (1 + t) / (10 + t)) over its updates t
+    clip_grad_norm: float = 0.0      # maximum global L2 norm of the gradient (0 = off)
 
     @property
     def soft_targets(self) -> bool:
@@ -116,6 +117,7 @@ _ENV = {
     "MX_EMA": ("ema", float),
     "MX_EMA_EVERY": ("ema_every", int),
     "MX_EMA_WARMUP": ("ema_warmup", _bool),
+    "MX_CLIP_GRAD_NORM": ("clip_grad_norm", float),
 }
 
 
@@ -170,6 +172,9 @@ def config_for(script: str, env: Optional[dict] = None,
         raise ValueError(f"MX_EMA is a decay in (0, 1) (0 = off), got {cfg.ema!r}")
     if cfg.ema_every < 1:
         raise ValueError(f"MX_EMA_EVERY is an interval of >= 1 optimizer steps, got {cfg.ema_every!r}")
+    if not cfg.clip_grad_norm >= 0 or cfg.clip_grad_norm == float("inf"):
+        raise ValueError(f"MX_CLIP_GRAD_NORM is a finite maximum gradient norm >= 0 (0 = off), got "
+                         f"{cfg.clip_grad_norm!r}")
     if cfg.nesterov and not cfg.momentum > 0:
         raise ValueError("MX_NESTEROV needs momentum > 0")
     if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:

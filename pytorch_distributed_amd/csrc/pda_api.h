@@ -308,6 +308,22 @@ int pda_sgd_seg(float* p, const float* g, float* buf, void* shadow, long long n,
                 const double* slab, const float* scale, const float* found_inf, int flags, int dt,
                 hipStream_t st);
 
+// ------------------------------------------------------------------ clip.hip
+// Host-side validation of a clip launch: blks (nblk BlkRow rows, `seg` unused) against a flat
+// gradient of n elements. 0 = good; otherwise the negative code that ops/native_ops.py turns into a
+// ValueError: -1 no rows or a missing buffer, -2 a row start negative or no multiple of 4, -3 a row
+// ends past n, -4 rows overlap, -5 max_norm not finite or not > 0, -6 a row's count outside
+// [1, SEG_CHUNK]
+int pda_clip_check(const BlkRow* blks, int nblk, long long n, float max_norm);
+// Global L2 norm of the rows' elements of g and torch's clip coefficient, one launch on stream st:
+// out[0] = inv * sqrt(sum g^2) (evaluated in double), out[1] = inv * min(1, max_norm / (out[0] +
+// 1e-6f)) in single precision, inv = inv_in[0] or 1 (inv_in null); found_inf (nullable) set:
+// out[1] = inv. slab: nblk doubles; cnt: one int32, zero (and left zero). The host rows are
+// validated first (pda_clip_check); nothing is launched on a bad table.
+int pda_grad_clip(const float* g, long long n, const void* blk_dev, const void* blk_host, int nblk,
+                  double* slab, int* cnt, float max_norm, const float* inv_in,
+                  const float* found_inf, float* out, hipStream_t st);
+
 // ------------------------------------------------------------------ mix.hip
 int pda_xent_soft(const float* logits, int B, int K, int ld_in, const long long* labels,
                   const long long* labels_b, float lam, float eps, float* loss_rows, float* loss,

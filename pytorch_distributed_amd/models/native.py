@@ -1191,9 +1191,10 @@ class NativeResNet(nn.Module):
             return self.native_forward(x, train=train, save=False)
 
     def make_optimizer(self, lr=0.1, momentum=0.9, weight_decay=1e-4, nesterov=False, lars=0.0,
-                       lars_eps=1e-8, param_groups=None) -> "NativeSGD":
+                       lars_eps=1e-8, param_groups=None, clip_grad_norm=0.0) -> "NativeSGD":
         return NativeSGD(self, lr=lr, momentum=momentum, weight_decay=weight_decay,
-                         nesterov=nesterov, lars=lars, lars_eps=lars_eps, param_groups=param_groups)
+                         nesterov=nesterov, lars=lars, lars_eps=lars_eps, param_groups=param_groups,
+                         clip_grad_norm=clip_grad_norm)
 
     def make_criterion(self, label_smoothing: float = 0.0) -> "NativeCrossEntropy":
         return NativeCrossEntropy(self, label_smoothing)

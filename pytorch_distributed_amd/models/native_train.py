@@ -124,7 +124,15 @@ class NativeSGD(torch.optim.Optimizer):
     trust coefficient. Parameters given to no group are frozen: their master weights, momentum and
     shadow are never touched. The groups' hyper-parameters may change between steps (``StepLR``); the
     table is re-uploaded when they do. Without these arguments the optimizer is the one-launch
-    ``sgd_flat`` step, unchanged."""
+    ``sgd_flat`` step, unchanged.
+
+    ``clip_grad_norm > 0`` clips the gradient by its global L2 norm
+    (``torch.nn.utils.clip_grad_norm_``) over every parameter of the groups, on the device: one
+    ``grad_clip`` launch (``csrc/clip.hip``) ahead of the update publishes the norm and the
+    coefficient, already multiplied by AMP's 1/scale, and the SGD launch takes that scalar as its
+    gradient scale -- no host sync, no second pass over the gradient. ``grad_norm`` is the
+    one-element device tensor holding the unscaled pre-clip norm of the last step that ran. The
+    clip keeps no state of its own. With 0 (the default) none of this exists."""
 
     @staticmethod
     def wants_segments(param_groups=None, nesterov=False, lars=0.0, **_kw) -> bool:
@@ -132,8 +140,14 @@ class NativeSGD(torch.optim.Optimizer):
         return param_groups is not None or bool(nesterov) or lars != 0
 
     def __init__(self, model: NativeResNet, lr=0.1, momentum=0.9, weight_decay=1e-4,
-                 dampening=0.0, nesterov=False, lars=0.0, lars_eps=1e-8, param_groups=None) -> None:
+                 dampening=0.0, nesterov=False, lars=0.0, lars_eps=1e-8, param_groups=None,
+                 clip_grad_norm=0.0) -> None:
         self._sealed = False
+        if (not isinstance(clip_grad_norm, (int, float)) or isinstance(clip_grad_norm, bool)
+                or not clip_grad_norm >= 0 or clip_grad_norm == float("inf")):
+            raise ValueError(f"NativeSGD: clip_grad_norm is a finite maximum norm >= 0 (0 = off), "
+                             f"got {clip_grad_norm!r}")
+        self.clip_grad_norm = float(clip_grad_norm)
         self.segmented = self.wants_segments(param_groups, nesterov, lars)
         if dampening != 0.0:
             raise ValueError("NativeSGD implements dampening=0 (reference setting)")
@@ -176,6 +190,17 @@ class NativeSGD(torch.optim.Optimizer):
             # ones), in group order; the device table is built once and re-uploaded on a change
             self._uploaded = self._hyper_rows()
             self._tables, _ = K.seg_tables(segments, self._uploaded, fp.device)
+        self.grad_norm = None
+        if self.clip_grad_norm > 0:
+            # every buffer of the clip launch, once: step() allocates nothing. The segmented step's
+            # block table covers the same tensors; the flat step gets one of its own
+            self._clip_tables = (self._tables if self.segmented else
+                                 K.seg_tables(segments, [{"lr": 0.0}] * len(segments), fp.device)[0])
+            self._clip_slab = torch.zeros(self._clip_tables.nblocks, dtype=torch.float64,
+                                          device=fp.device)
+            self._clip_cnt = torch.zeros(1, dtype=torch.int32, device=fp.device)
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=fp.device)
+            self.grad_norm = self._clip_out[0:1]
 
     def add_param_group(self, param_group) -> None:
         if getattr(self, "_sealed", False):
@@ -221,6 +246,11 @@ class NativeSGD(torch.optim.Optimizer):
             # and SGD skips parameters without a gradient -- the flat gradient still holds the
             # previous step's values (no memset), so applying it would be a stale update
             return
+        if self.clip_grad_norm > 0:
+            # norm and coefficient on the device; the update unscales AND clips by out[1]
+            K.grad_clip(m.flat_grad, self._clip_tables, self.clip_grad_norm, self._clip_slab,
+                        self._clip_cnt, self._clip_out, inv_scale=inv_scale, found_inf=found_inf)
+            inv_scale = self._clip_out[1:2]
         if self.segmented:
             self._launch_segments(inv_scale, found_inf)
         else:

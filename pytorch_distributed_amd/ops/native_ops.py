@@ -30,7 +30,7 @@ __all__ = [
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
     "aug_draw", "aug_resize_dev", "aug_record_bytes",
-    "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg",
+    "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg", "grad_clip",
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
 ]
 
@@ -1423,6 +1423,45 @@ def sgd_seg(p, g, buf, shadow, tables: SegTables, initialized: bool, inv_scale=N
                                ptr(tables.slab), ptr(inv_scale), ptr(found_inf), flags, dt,
                                stream(p.device))
     _seg_check(rc, "sgd_seg")
+
+
+# ------------------------------------------------------------------ gradient clipping (csrc/clip.hip)
+_CLIP_ERRORS = {-1: "no block rows or a missing buffer", -2: "a row start is negative or no multiple of 4",
+                -3: "a row ends past the gradient", -4: "rows overlap",
+                -5: "max_norm must be finite and > 0",
+                -6: "a row's count lies outside [1, SEG_CHUNK]"}
+
+
+def grad_clip(g, tables: SegTables, max_norm: float, slab, cnt, out, inv_scale=None,
+              found_inf=None) -> None:
+    """Global-norm gradient clipping, the device half (one launch, no host sync): over the block
+    rows of ``tables`` (:func:`seg_tables`; elements of ``g`` in no row are never read),
+    ``out[0] = inv * sqrt(sum g^2)`` -- the unscaled norm, summed in double in a fixed order -- and
+    ``out[1] = inv * min(1, max_norm / (out[0] + 1e-6))`` in single precision, which the SGD
+    launches take as their ``inv_scale``. ``inv = inv_scale[0]`` (1 when None); with ``found_inf``
+    set ``out[1] = inv``. ``slab``: f64, one entry per block row; ``cnt``: one int32, zero (the
+    kernel leaves it zero); ``out``: f32[2]. Bad arguments raise ValueError and launch nothing."""
+    _seg_flat("grad_clip", g.numel(), tables.device, g=g)
+    dev = tables.device
+    if g.dtype != torch.float32:
+        raise ValueError("grad_clip: g is f32")
+    for name, t, dtype, least in (("slab", slab, torch.float64, tables.nblocks),
+                                  ("cnt", cnt, torch.int32, 1), ("out", out, torch.float32, 2),
+                                  ("inv_scale", inv_scale, torch.float32, 1),
+                                  ("found_inf", found_inf, torch.float32, 1)):
+        if t is None and name in ("inv_scale", "found_inf"):
+            continue
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype
+                or not t.is_contiguous() or t.numel() < least or t.data_ptr() % t.element_size()):
+            raise ValueError(f"grad_clip: {name} must be a contiguous {dtype} tensor of at least "
+                             f"{least} element(s) on {dev}")
+    rc = ext.lib().pda_grad_clip(ptr(g), g.numel(), ptr(tables.blk_dev),
+                                 C.cast(tables.blk_host, C.c_void_p), tables.nblocks, ptr(slab),
+                                 ptr(cnt), float(max_norm), ptr(inv_scale), ptr(found_inf), ptr(out),
+                                 stream(g.device))
+    if rc < 0:
+        raise ValueError(f"grad_clip: {_CLIP_ERRORS.get(rc, f'bad arguments ({rc})')}")
+    check(rc, "grad_clip")
 
 
 # ------------------------------------------------------------------ weight EMA (csrc/ema.hip)

@@ -177,12 +177,21 @@ class DataParallel(nn.Module):
             raise ValueError(SEGMENTED_REFUSAL.format(
                 what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
 
+    def _refuse_clip(self, clip: float) -> None:
+        """As :meth:`_refuse_segmented`, for gradient clipping (``clip_grad_norm > 0``)."""
+        if clip and (self.replicas or (self.force_replay and self._native)):
+            from ..runtime.graphs import CLIP_REFUSAL
+            raise ValueError(CLIP_REFUSAL.format(
+                what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+
     def make_optimizer(self, **kw):
+        self._refuse_clip(kw.get("clip_grad_norm", 0.0))
         if self._native:
             from ..models.native import NativeSGD
             self._refuse_segmented(NativeSGD.wants_segments(**kw))
             opts = [m.make_optimizer(**kw) for m in self.all_modules]
             return ReplicatedSGD(opts) if self.replicas else opts[0]
+        kw.pop("clip_grad_norm", None)       # (torch optimizers: the trainer clips before step())
         groups = kw.pop("param_groups", None)
         params = groups if groups is not None else self.module.parameters()
         if kw.get("lars", 0) > 0 or any(g.get("lars", 0) > 0 for g in groups or []):

@@ -143,6 +143,14 @@ SEGMENTED_REFUSAL = ("{what} cannot run the segmented optimizer (parameter group
                      "MX_NESTEROV / MX_NO_BN_DECAY / MX_LARS / param_groups")
 
 
+# Gradient clipping (MX_CLIP_GRAD_NORM) lives inside NativeSGD.step(), so MX_GRAPH=1 captures it; the
+# replicated optimizers of DataParallel's replica graphs are not wired for it.
+CLIP_REFUSAL = ("{what} cannot run MX_CLIP_GRAD_NORM: the replicated optimizers of the DataParallel "
+                "replica graphs do not clip. Run on one device without DataParallel's replay (the "
+                "single-GPU script, with or without MX_GRAPH=1, and the DDP scripts work), or drop "
+                "MX_CLIP_GRAD_NORM / clip_grad_norm")
+
+
 class GraphedNativeStep:
     """Capture-once / replay-per-step driver of :func:`native_train_step`.
 

@@ -162,6 +162,11 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     graphed = None if soft else _graphed_step(model, optimizer, ctx)
     ema = ctx.extra.get("ema")          # MX_EMA: the weight average follows every optimizer step
     sb = ctx.extra.get("step_busy")     # device-busy fallback (utils/gpu_util.py StepBusy)
+    # MX_CLIP_GRAD_NORM: the native optimizer clips inside its step (csrc/clip.hip) and keeps the
+    # norm in optimizer.grad_norm; torch optimizers are clipped here, before optimizer.step()
+    clip_params = grad_norm = None
+    if cfg.clip_grad_norm > 0 and not hasattr(optimizer, "clip_grad_norm"):
+        clip_params = [p for g in optimizer.param_groups for p in g["params"]]
     for step, (samples, labels) in dataloader.iter_from(start_step):
         if ctx.cfg.script == "single" and cfg.log_every and step % cfg.log_every == 0:
             print("epoch: {}, step: {}".format(epoch, step), flush=True)
@@ -186,6 +191,9 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
                 outputs = model(samples)
                 loss = criterion(outputs, labels, *soft_args)
             scaler.scale(loss).backward()
+            if clip_params is not None:
+                scaler.unscale_(optimizer)
+                grad_norm = torch.nn.utils.clip_grad_norm_(clip_params, cfg.clip_grad_norm)
             scaler.step(optimizer)
             scaler.update()
             optimizer.zero_grad()
@@ -196,6 +204,8 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             loss = criterion(outputs.float() if outputs.dtype != torch.float32 else outputs, labels,
                              *soft_args)
             loss.backward()
+            if clip_params is not None:
+                grad_norm = torch.nn.utils.clip_grad_norm_(clip_params, cfg.clip_grad_norm)
             optimizer.step()
         if ema is not None:
             ema.update()
@@ -216,6 +226,10 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
                           flush=True)
                 go_suspend()
     prof.close()
+    if cfg.clip_grad_norm > 0:
+        # the pre-clip norm of the epoch's last step: a device tensor, read by run() after validation
+        ctx.extra["grad_norm"] = (getattr(optimizer, "grad_norm", None) if clip_params is None
+                                  else grad_norm)
     return steps
 
 
@@ -362,12 +376,23 @@ def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
     grouped SGD (:func:`~pytorch_distributed_amd.optim.build_param_groups`): the segmented kernel on
     the native engine, ``torch.optim.SGD`` or :class:`~pytorch_distributed_amd.optim.LARS` on the
     torch engine. The captured-step paths refuse the segmented optimizer (ValueError, raised here:
-    before training starts)."""
+    before training starts). ``MX_CLIP_GRAD_NORM`` goes to the native optimizer, which clips inside
+    its step; the torch optimizers are clipped by :func:`train`. DataParallel over several devices
+    (or with ``PDA_DP_FORCE_REPLAY=1``) refuses it, here as well."""
     inner = _factory_owner(model, "make_optimizer")
     native = hasattr(inner, "make_optimizer")
+    clip = {}
+    if cfg.clip_grad_norm > 0:
+        if getattr(model, "replicas", None) or (getattr(model, "force_replay", False)
+                                                and getattr(model, "_native", False)):
+            from .runtime.graphs import CLIP_REFUSAL
+            raise ValueError(CLIP_REFUSAL.format(
+                what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+        clip = dict(clip_grad_norm=cfg.clip_grad_norm)
     if not (cfg.nesterov or cfg.no_bn_decay or cfg.lars > 0):
         if native:
-            return inner.make_optimizer(lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay)
+            return inner.make_optimizer(lr=cfg.lr, momentum=cfg.momentum,
+                                        weight_decay=cfg.weight_decay, **clip)
         return torch.optim.SGD(model.parameters(), lr=cfg.lr, momentum=cfg.momentum,
                                weight_decay=cfg.weight_decay)
     from .optim import LARS, build_param_groups
@@ -377,7 +402,7 @@ def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
     groups = build_param_groups(_unwrap(model), cfg.weight_decay, cfg.no_bn_decay, cfg.lars)
     kw = dict(lr=cfg.lr, momentum=cfg.momentum, weight_decay=cfg.weight_decay, nesterov=cfg.nesterov)
     if native:      # (DataParallel over several devices raises the same ValueError)
-        return inner.make_optimizer(param_groups=groups, **kw)
+        return inner.make_optimizer(param_groups=groups, **kw, **clip)
     if cfg.lars > 0:
         return LARS(groups, **kw)
     return torch.optim.SGD(groups, **kw)
@@ -508,6 +533,8 @@ def run(cfg: RunConfig, mode: str, local_rank: int = 0, nprocs: Optional[int] = 
         # MX_EMA: a second pass over the averaged weights, which then decide (and are) best.pt
         with ema.swapped() if ema is not None else contextlib.nullcontext():
             more = {}
+            if cfg.clip_grad_norm > 0 and ctx.extra.get("grad_norm") is not None:
+                more["grad_norm"] = float(ctx.extra["grad_norm"])
             if ema is not None:
                 more["ema_acc1"] = validate(val_loader, model, criterion, epoch, ctx, prefix="EMA ")
             t2 = time.time()
