@@ -26,7 +26,7 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = os.environ.get("PDA_ARCH", "gfx950")
 
 KERNEL_SRCS = ["conv_gemm.hip", "bn.hip", "misc.hip", "stem.hip", "wgrad_tap.hip", "augment.hip",
-               "optim.hip", "mix.hip", "ema.hip", "clip.hip"]
+               "optim.hip", "mix.hip", "ema.hip", "clip.hip", "erase.hip"]
 COMM_SRCS = ["comm/rccl_comm.cpp", "comm/reducer.cpp"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"]
 
@@ -41,8 +41,10 @@ def _newer(src: Path, obj: Path, deps) -> bool:
 # per-source flags: the conv kernels keep their operand-prologue math in scalar f32 FMAs, which
 # beside MFMAs issue far cheaper than the v_pk_fma_f32 the SLP vectorizer would form
 # augment.hip evaluates PIL's resampling geometry in double; without FMA contraction its integer tap
-# bounds are those of a float64 numpy evaluation of the same expressions (tests/aug_refs.py)
-FILE_FLAGS = {"conv_gemm.hip": ["-fno-slp-vectorize"], "augment.hip": ["-ffp-contract=off"]}
+# bounds are those of a float64 numpy evaluation of the same expressions (tests/aug_refs.py);
+# erase.hip draws its boxes in double for the same reason (tests/erase_refs.py)
+FILE_FLAGS = {"conv_gemm.hip": ["-fno-slp-vectorize"], "augment.hip": ["-ffp-contract=off"],
+              "erase.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: Path, obj: Path, extra, verbose: bool) -> None:

@@ -60,6 +60,7 @@ class RunConfig:
     ema_every: int = 1               # EMA update interval in optimizer steps
     ema_warmup: bool = True          # EMA decay min(decay, (1 + t) / (10 + t)) over its updates t
     clip_grad_norm: float = 0.0      # maximum global L2 norm of the gradient (0 = off)
+    random_erase: float = 0.0        # random-erasing probability p in [0, 1] (0 = off)
 
     @property
     def soft_targets(self) -> bool:
@@ -118,6 +119,7 @@ _ENV = {
     "MX_EMA_EVERY": ("ema_every", int),
     "MX_EMA_WARMUP": ("ema_warmup", _bool),
     "MX_CLIP_GRAD_NORM": ("clip_grad_norm", float),
+    "MX_RANDOM_ERASE": ("random_erase", float),
 }
 
 
@@ -175,6 +177,9 @@ def config_for(script: str, env: Optional[dict] = None,
     if not cfg.clip_grad_norm >= 0 or cfg.clip_grad_norm == float("inf"):
         raise ValueError(f"MX_CLIP_GRAD_NORM is a finite maximum gradient norm >= 0 (0 = off), got "
                          f"{cfg.clip_grad_norm!r}")
+    if not 0 <= cfg.random_erase <= 1:
+        raise ValueError(f"MX_RANDOM_ERASE is a probability in [0, 1] (0 = off), got "
+                         f"{cfg.random_erase!r}")
     if cfg.nesterov and not cfg.momentum > 0:
         raise ValueError("MX_NESTEROV needs momentum > 0")
     if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:

@@ -337,6 +337,24 @@ int pda_xent_soft(const float* logits, int B, int K, int ld_in, const long long*
 int pda_batch_mix(const void* x, void* out, int B, int S, int dt, int layout, int mode, float lam,
                   float oml, int y1, int y2, int x1, int x2, int grid_cap, hipStream_t st);
 
+// ------------------------------------------------------------------ erase.hip
+// Random-erasing boxes of a batch of B SxS images, one launch on stream st: boxes (device int32
+// [B][4], 4-byte aligned) row b = (y1, y2, x1, x2), half-open, all zeros when sample b is left alone.
+// bkey: the batch's key (erase.py batch_key); p: the probability; s0 <= s1: the scale bounds (>= 0);
+// l0 <= l1: the LOGARITHMS of the ratio bounds. Returns -2 and launches nothing for B <= 0, S <= 0,
+// S > 32768, p outside [0, 1] or NaN, descending or non-finite bounds, a negative scale bound, or a
+// null or misaligned table.
+int pda_erase_draw(int B, int S, unsigned bkey, double p, double s0, double s1, double l0, double l1,
+                   int* boxes, hipStream_t st);
+// x (in place): layout 0 = s2d [B][S/2][S/2][16] (dt f32 / bf16 / f16, S even), 1 = NCHW f32; pixels
+// with y1 <= y < y2 and x1 <= x < x2 of sample b's row of boxes (device int32 [B][4], as
+// pda_erase_draw writes it; clamped to [0, S] by the kernel, an empty box skipped) become +0.0 in
+// all three channels, every other bit stays. Returns -2 for arguments the kernels must never see: x
+// not 16-byte or boxes not 4-byte aligned, odd S in layout 0, a dtype other than f32 in layout 1.
+// ``grid_cap`` as in pda_batch_mix: the most blocks to launch (0: the natural grid).
+int pda_batch_erase(void* x, const int* boxes, int B, int S, int dt, int layout, int grid_cap,
+                    hipStream_t st);
+
 // ------------------------------------------------------------------ ema.hip
 // Host-side validation of a range table. 0 = good; otherwise the negative code that
 // ops/native_ops.py turns into a ValueError:

@@ -32,6 +32,7 @@ __all__ = [
     "aug_draw", "aug_resize_dev", "aug_record_bytes",
     "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg", "grad_clip",
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
+    "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
 ]
 
 
@@ -1733,6 +1734,96 @@ def batch_mix(x, out, layout: int, mode: int, lam: float, box=None) -> None:
     lam32, oml32 = mix_weights(lam)
     check(ext.lib().pda_batch_mix(ptr(x), ptr(out), B, S, dt_of(x), layout, mode, lam32, oml32, *box,
                                   0, stream(x.device)), "batch_mix")
+
+
+# ------------------------------------------------------------------ random erasing of a batch
+ERASE_SCALE, ERASE_RATIO = (0.02, 0.33), (0.3, 3.3)      # torchvision's RandomErasing defaults
+
+
+def erase_bounds(p: float, scale, ratio) -> Tuple[float, float, float, float, float]:
+    """``(p, s0, s1, l0, l1)`` of a random-erasing draw, validated: the probability, the scale
+    bounds and the LOGARITHMS of the ratio bounds, as ``pda_erase_draw`` takes them (and as
+    ``erase.draw_erase`` evaluates them: one ``math.log`` per bound, on the host)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"erase_draw: p must be a probability in [0, 1], got {p!r}")
+    if len(scale) != 2 or len(ratio) != 2:
+        raise ValueError(f"erase_draw: scale {scale!r} and ratio {ratio!r} must be (low, high) pairs")
+    s0, s1, r0, r1 = float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1])
+    if not (math.isfinite(s0) and math.isfinite(s1) and 0.0 <= s0 <= s1):
+        raise ValueError(f"erase_draw: scale {scale!r} must be finite, >= 0 and ascending")
+    if not (math.isfinite(r0) and math.isfinite(r1) and 0.0 < r0 <= r1):
+        raise ValueError(f"erase_draw: ratio {ratio!r} must be finite, > 0 and ascending")
+    return p, s0, s1, math.log(r0), math.log(r1)
+
+
+def _erase_table_check(what: str, boxes, B: Optional[int] = None) -> int:
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 4 or not boxes.is_contiguous():
+        raise ValueError(f"{what}: boxes must be a contiguous int32 [B, 4] tensor, got "
+                         f"{tuple(boxes.shape)} {boxes.dtype}")
+    if boxes.shape[0] < 1 or (B is not None and boxes.shape[0] != B):
+        raise ValueError(f"{what}: boxes has {boxes.shape[0]} rows for a batch of {B if B is not None else '>= 1'}")
+    return boxes.shape[0]
+
+
+def erase_draw(boxes, S: int, bkey: int, p: float, scale=ERASE_SCALE, ratio=ERASE_RATIO) -> None:
+    """Draw the random-erasing boxes of a batch on the device (one launch, csrc/erase.hip
+    ``erase_draw_kernel``) into ``boxes``, a device int32 [B, 4] table: row b = (y1, y2, x1, x2),
+    half-open, of the sample at batch position b, all zeros when it is left alone. ``bkey``:
+    ``erase.batch_key(seed, rank, epoch, step)``; ``erase.draw_erase`` is the host mirror."""
+    B = _erase_table_check("erase_draw", boxes)
+    p, s0, s1, l0, l1 = erase_bounds(p, scale, ratio)
+    if int(S) != S or not 1 <= S <= AUG_MAX_SIDE:
+        raise ValueError(f"erase_draw: image side {S!r} outside 1..{AUG_MAX_SIDE}")
+    if boxes.device.type != "cuda":
+        raise ValueError("erase_draw runs on a GPU; the table is on " + str(boxes.device))
+    if boxes.data_ptr() % 4:
+        raise ValueError("erase_draw: boxes must be 4-byte aligned")
+    check(ext.lib().pda_erase_draw(B, int(S), int(bkey) & 0xFFFFFFFF, p, s0, s1, l0, l1, ptr(boxes),
+                                   stream(boxes.device)), "erase_draw")
+
+
+def batch_erase_check(x, boxes, layout: int) -> Tuple[int, int]:
+    """Host-side validation of a :func:`batch_erase` call; returns (B, S). Pure Python (the kernel
+    library is not loaded), run before the launch. The table's VALUES are not read: the kernel
+    clamps every box to the image."""
+    if layout == AUG_S2D:
+        if x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] != 16:
+            raise ValueError(f"batch_erase: s2d input must be [B, S/2, S/2, 16], got {tuple(x.shape)}")
+        if x.dtype not in ext.DT:
+            raise ValueError(f"batch_erase: unsupported dtype {x.dtype}")
+        S = 2 * x.shape[1]
+    elif layout == AUG_NCHW:
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise ValueError(f"batch_erase: NCHW input must be [B, 3, S, S], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"batch_erase: the NCHW layout is f32, got {x.dtype}")
+        S = x.shape[2]
+    else:
+        raise ValueError(f"batch_erase: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
+    B = x.shape[0]
+    if B < 1 or S < 1 or S > (AUG_MAX_SIDE if layout == AUG_S2D else 26000):
+        raise ValueError(f"batch_erase: empty batch or image side {S} out of range")
+    if not x.is_contiguous():
+        raise ValueError("batch_erase: x must be contiguous")
+    _erase_table_check("batch_erase", boxes, B)
+    if boxes.device != x.device:
+        raise ValueError(f"batch_erase: boxes on {boxes.device}, the batch on {x.device}")
+    return B, S
+
+
+def batch_erase(x, boxes, layout: int) -> None:
+    """Set the pixels inside each sample's box to +0.0, in place (one launch, csrc/erase.hip).
+    ``layout``: ``AUG_S2D`` [B, S/2, S/2, 16] (f32 / bf16 / f16) or ``AUG_NCHW`` [B, 3, S, S] f32;
+    ``boxes``: device int32 [B, 4] rows (y1, y2, x1, x2), half-open, as :func:`erase_draw` writes
+    them. Every bit outside the boxes stays, the s2d padding slots included."""
+    B, S = batch_erase_check(x, boxes, layout)
+    if x.device.type != "cuda":
+        raise ValueError("batch_erase runs on a GPU; the batch is on " + str(x.device))
+    if x.data_ptr() % 16 or boxes.data_ptr() % 4:
+        raise ValueError("batch_erase: x must be 16-byte aligned (boxes 4-byte)")
+    check(ext.lib().pda_batch_erase(ptr(x), ptr(boxes), B, S, dt_of(x), layout, 0, stream(x.device)),
+          "batch_erase")
 
 
 AUG_TRAIN, AUG_VAL = 0, 1

@@ -145,6 +145,18 @@ def _batch_mixer(ctx: Context):
     return mixer
 
 
+def _batch_eraser(ctx: Context):
+    """``MX_RANDOM_ERASE``: the run's :class:`~pytorch_distributed_amd.erase.BatchEraser` (kept on
+    the context: one box table serves every epoch), else None."""
+    if not ctx.cfg.random_erase > 0:
+        return None
+    eraser = ctx.extra.get("eraser")
+    if eraser is None:
+        from .erase import BatchEraser
+        eraser = ctx.extra["eraser"] = BatchEraser(ctx.cfg, ctx)
+    return eraser
+
+
 def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: Context,
           start_step: int, best_acc: float, save_path: Path) -> int:
     """One epoch of training (reference ``restnet_ddp.py:19-47``). Returns steps run."""
@@ -154,6 +166,7 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     scaler = ctx.scaler
     soft = cfg.soft_targets
     mixer = _batch_mixer(ctx)
+    eraser = _batch_eraser(ctx)
     from .utils.metrics import StepProfiler
     prof = StepProfiler(int(os.environ.get("MX_PROFILE", "0") or 0) if epoch == 0 else 0, save_path,
                         ctx.rank)
@@ -174,6 +187,11 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             sb.begin()
         samples = samples.to(ctx.device, non_blocking=True)
         labels = labels.to(ctx.device, non_blocking=True)
+        if eraser is not None:
+            # per-sample transform, so before the mixing (torchvision's order); in place: every
+            # loader makes a fresh batch per step, and the captured steps (MX_GRAPH=1, DataParallel)
+            # copy the batch they are handed on this stream, after the erase
+            samples = eraser(samples, epoch, step)
         soft_args = ()                   # (labels_b, lam): the criterion's two further arguments
         if soft:
             labels_b, lam = None, 1.0
