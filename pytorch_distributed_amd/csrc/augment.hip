@@ -30,7 +30,7 @@
 // tap loops filter these three planes and the store stage converts once per output pixel:
 //   R = Y + 1.402 cr, G = Y - 0.344136 cb - 0.714136 cr, B = Y + 1.772 cb, clamped to [0, 255],
 // then normalised as above. A grey image has filtered chroma of exactly 0 and R = G = B = Y.
-#include "common.h"
+#include "batch_image.h"
 #include "pda_api.h"
 
 namespace {
@@ -271,9 +271,9 @@ __global__ __launch_bounds__(AUG_NT) void aug_resize_kernel(const uint8_t* __res
 // One thread per sample: looks the sample's record up in the dataset index [N][4] = (byte offset, H,
 // W, label) and writes the rows of the tables aug_resize_kernel reads, plus the label. Train mode is
 // data/folder.py train_crop_params (RandomResizedCrop + flip) in double; val mode is val_crop_params.
-// The uniforms are counter-based: u(k) = hash32(ekey ^ (k+1)*0x27D4EB2F) / 2^32 with
+// The uniforms are counter-based (batch_image.h): u(k) = counter_u01(ekey, k) with
 //   key = hash32(id*2654435761 + salt), salt = (seed*97 + split_id)*0x632BE5AB   (as the synthetic data)
-//   ekey = hash32(key ^ (epoch*0x9E3779B9 + 0x85EBCA6B))
+//   ekey = counter_subkey(key, epoch)
 // and fixed counters: attempt a draws area 4a, ratio 4a+1, row 4a+2, column 4a+3; the flip is 40. A
 // sample's crop therefore depends on (seed, split, epoch, id) alone, not on where in which batch of
 // which rank it is drawn. tests/packed_refs.py evaluates the same expressions in Python float64.
@@ -283,10 +283,6 @@ struct AugDraw {
   int mode, S, resize;
   double s0, s1, l0, l1, r0, r1;   // scale bounds, log ratio bounds, ratio bounds
 };
-
-__device__ __forceinline__ double aug_u(uint32_t ekey, uint32_t k) {
-  return (double)hash32(ekey ^ ((k + 1u) * 0x27D4EB2Fu)) * (1.0 / 4294967296.0);   // exact in double
-}
 
 __global__ __launch_bounds__(AUG_NT) void aug_draw_kernel(const long long* __restrict__ ids,
                                                           const long long* __restrict__ index,
@@ -306,18 +302,18 @@ __global__ __launch_bounds__(AUG_NT) void aug_draw_kernel(const long long* __res
   int flip = 0;
   if (d.mode == 0) {
     const uint32_t key = hash32((uint32_t)id * 2654435761u + d.salt);
-    const uint32_t ekey = hash32(key ^ (d.epoch * 0x9E3779B9u + 0x85EBCA6Bu));
+    const uint32_t ekey = counter_subkey(key, d.epoch);
     const double area = (double)(W * H);
     int w = 0, h = 0, i = 0, j = 0;
     bool ok = false;
     for (uint32_t a = 0; a < 10 && !ok; ++a) {
-      const double target = area * (d.s0 + (d.s1 - d.s0) * aug_u(ekey, 4 * a));
-      const double ar = exp(d.l0 + (d.l1 - d.l0) * aug_u(ekey, 4 * a + 1));
+      const double target = area * (d.s0 + (d.s1 - d.s0) * counter_u01(ekey, 4 * a));
+      const double ar = exp(d.l0 + (d.l1 - d.l0) * counter_u01(ekey, 4 * a + 1));
       w = (int)rint(sqrt(target * ar));
       h = (int)rint(sqrt(target / ar));
       if (0 < w && w <= W && 0 < h && h <= H) {
-        i = (int)(aug_u(ekey, 4 * a + 2) * (double)(H - h + 1));
-        j = (int)(aug_u(ekey, 4 * a + 3) * (double)(W - w + 1));
+        i = (int)(counter_u01(ekey, 4 * a + 2) * (double)(H - h + 1));
+        j = (int)(counter_u01(ekey, 4 * a + 3) * (double)(W - w + 1));
         ok = true;
       }
     }
@@ -342,7 +338,7 @@ __global__ __launch_bounds__(AUG_NT) void aug_draw_kernel(const long long* __res
     y0 = (double)i;
     x1 = (double)(j + w);
     y1 = (double)(i + h);
-    flip = aug_u(ekey, 40) < 0.5 ? 1 : 0;
+    flip = counter_u01(ekey, 40) < 0.5 ? 1 : 0;
   } else {
     int nw, nh;
     if (W <= H) {

@@ -27,24 +27,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int CLIP_CHUNK = 4096;   // most elements of one block row (optim.hip SEG_CHUNK)
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the block in a fixed order; every thread holds the result (red: NT / 64 doubles)
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NT / 64; ++w) t += red[w];
-  return t;
-}
 
 __global__ __launch_bounds__(NT) void grad_clip_kernel(const float* __restrict__ g,
                                                        const BlkRow* __restrict__ blks, double* slab,
@@ -60,7 +42,7 @@ __global__ __launch_bounds__(NT) void grad_clip_kernel(const float* __restrict__
   const f32x4* g4 = reinterpret_cast<const f32x4*>(g + b.first);
   // a full chunk is U 16-byte loads per lane: all issued before the first use (one dependent
   // round per block instead of U), accumulated in ascending order; a lane past the end adds +0
-  constexpr int U = CLIP_CHUNK / (4 * NT);
+  constexpr int U = FLAT_CHUNK / (4 * NT);
   f32x4 gv[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -75,7 +57,7 @@ __global__ __launch_bounds__(NT) void grad_clip_kernel(const float* __restrict__
     const float gv = g[b.first + (nv << 2) + threadIdx.x];
     s += (double)gv * (double)gv;
   }
-  const double tot = block_sum_f64(s, red);
+  const double tot = block_sum_f64<NT>(s, red);
   if (threadIdx.x == 0) {
     // publish: write-through store, drained by this lane before its arrival (bn.hip, the hand-off)
     __hip_atomic_store(slab + blockIdx.x, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -92,7 +74,7 @@ __global__ __launch_bounds__(NT) void grad_clip_kernel(const float* __restrict__
   if (!s_last) return;
   double a = 0.0;
   for (int k = threadIdx.x; k < (int)gridDim.x; k += NT) a += slab[k];   // ascending, fixed share
-  const double sum = block_sum_f64(a, red);
+  const double sum = block_sum_f64<NT>(a, red);
   if (threadIdx.x == 0) {
     const float inv = inv_in ? inv_in[0] : 1.f;
     const float norm = (float)((double)inv * sqrt(sum));
@@ -115,7 +97,7 @@ int pda_clip_check(const BlkRow* blks, int nblk, long long n, float max_norm) {
   for (int i = 0; i < nblk; ++i) {
     const BlkRow& b = blks[i];
     if (b.first < 0 || (b.first & 3)) return -2;
-    if (b.count <= 0 || b.count > CLIP_CHUNK) return -6;
+    if (b.count <= 0 || b.count > FLAT_CHUNK) return -6;
     if (b.first > n || b.count > n - b.first) return -3;
     ascending &= b.first >= prev_end;
     prev_end = b.first + b.count;

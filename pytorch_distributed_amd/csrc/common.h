@@ -182,6 +182,14 @@ __device__ __forceinline__ float ld_any(const void* base, size_t i, int dt) {
   const u16 h = reinterpret_cast<const u16*>(base)[i];
   return dt == DT_BF16 ? bf16_to_f32(h) : f16_to_f32(h);
 }
+// the 16-bit shadow of an f32 master value (optimizer, EMA exchange): torch's cast, dt = bf16 | f16
+__device__ __forceinline__ u16 cvt16_rt(float f, int dt) {
+  return dt == DT_BF16 ? f32_to_bf16(f) : f32_to_f16(f);
+}
+
+// most elements one workgroup of a flat-buffer kernel (optim.hip, clip.hip, ema.hip) handles; the
+// host cuts the block tables by it (ops/native_ops.py FLAT_CHUNK)
+constexpr int FLAT_CHUNK = 4096;
 
 // ---- fast unsigned division by a runtime constant (n < 2^31) --------------------------------
 struct FastDiv {
@@ -211,6 +219,23 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// sum over a block of NT threads in a fixed order (each wave's shuffle tree, then the waves
+// ascending); every thread holds the result. red: NT / 64 doubles of LDS, free again after the
+// caller's next __syncthreads()
+template <int NT> __device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) t += red[w];
+  return t;
 }
 
 // XCD-aware bijective remap of a 1-D block index: consecutive *logical* tiles land on the same

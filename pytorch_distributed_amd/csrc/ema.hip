@@ -3,8 +3,8 @@
 // A *range* (EmaRange) is an averaged buffer e, the live buffer p it follows, an optional 16-bit
 // shadow of p and an element count; the parameters and the BatchNorm statistics are two ranges of
 // one launch. The launcher validates the ranges on the host (pda_ema_check), cuts each into chunks
-// of at most EMA_CHUNK elements, one workgroup per chunk, and passes the table by value: there is no
-// device table to upload, so a launch allocates nothing and copies nothing.
+// of at most FLAT_CHUNK (common.h) elements, one workgroup per chunk, and passes the table by value:
+// there is no device table to upload, so a launch allocates nothing and copies nothing.
 //
 //   EMA_LERP : e = fmaf(w, p - e, e) in f32; p is only read. Where p == e the difference is +0 and
 //              e keeps its bits (an e of -0 excepted: -0 + +0 = +0); w = 0 keeps e, w = 1 gives
@@ -27,7 +27,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int EMA_CHUNK = 4096;    // elements per block (ops/native_ops.py EMA_CHUNK)
 constexpr int EMA_MAX_ROWS = 8;    // ranges per launch (the launcher splits longer tables)
 enum EmaMode : int { EMA_LERP = 0, EMA_COPY = 1, EMA_SWAP = 2 };
 
@@ -45,11 +44,6 @@ struct EmaTable {
   int nrows;
 };
 
-__device__ __forceinline__ u16 ema_cvt16(uint32_t bits, int dt) {
-  const float f = __uint_as_float(bits);
-  return dt == DT_BF16 ? f32_to_bf16(f) : f32_to_f16(f);
-}
-
 __device__ __forceinline__ uint32_t ema_lerp(uint32_t e, uint32_t p, float w) {
   const float ef = __uint_as_float(e);
   return __float_as_uint(__builtin_fmaf(w, __uint_as_float(p) - ef, ef));
@@ -63,10 +57,10 @@ __global__ __launch_bounds__(NT) void ema_kernel(const EmaTable t, float w, int 
 #pragma unroll
   for (int k = 1; k < EMA_MAX_ROWS; ++k)
     if (k < t.nrows && (long long)blockIdx.x >= t.rows[k].blk0) r = t.rows[k];
-  const long long first = ((long long)blockIdx.x - r.blk0) * EMA_CHUNK;
+  const long long first = ((long long)blockIdx.x - r.blk0) * FLAT_CHUNK;
   const long long left = r.count - first;
   if (left <= 0) return;   // (the launcher sizes the grid exactly: not reached)
-  const int count = left < EMA_CHUNK ? (int)left : EMA_CHUNK;
+  const int count = left < FLAT_CHUNK ? (int)left : FLAT_CHUNK;
   uint32_t* e = r.e + first;
   uint32_t* p = r.p + first;
   u16* shadow = (MODE == EMA_SWAP && r.shadow) ? r.shadow + first : nullptr;
@@ -89,7 +83,7 @@ __global__ __launch_bounds__(NT) void ema_kernel(const EmaTable t, float w, int 
       if (shadow) {
         u16 h[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) h[k] = ema_cvt16(ev[k], dt);
+        for (int k = 0; k < 4; ++k) h[k] = cvt16_rt(__uint_as_float(ev[k]), dt);
         reinterpret_cast<uint2*>(shadow)[i] = *reinterpret_cast<uint2*>(h);
       }
     }
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(NT) void ema_kernel(const EmaTable t, float w, int 
       const uint32_t ev = e[i];
       e[i] = pv;
       p[i] = ev;
-      if (shadow) shadow[i] = ema_cvt16(ev, dt);
+      if (shadow) shadow[i] = cvt16_rt(__uint_as_float(ev), dt);
     }
   }
 }
@@ -128,7 +122,7 @@ int pda_ema_check(const EmaRange* rows, int nrows, int mode, float w, int dt) {
     const bool sh = mode == EMA_SWAP && r.shadow;
     if (sh && dt != DT_BF16 && dt != DT_F16) return -1;
     if (((uintptr_t)r.e & 15) || ((uintptr_t)r.p & 15) || (sh && ((uintptr_t)r.shadow & 7))) return -2;
-    blocks += (r.count + EMA_CHUNK - 1) / EMA_CHUNK;
+    blocks += (r.count + FLAT_CHUNK - 1) / FLAT_CHUNK;
     if (blocks > 0x7fffffffLL) return -3;
     span.emplace_back((uintptr_t)r.e, (uintptr_t)r.e + 4 * (uintptr_t)r.count);
     span.emplace_back((uintptr_t)r.p, (uintptr_t)r.p + 4 * (uintptr_t)r.count);
@@ -140,7 +134,7 @@ int pda_ema_check(const EmaRange* rows, int nrows, int mode, float w, int dt) {
   return 0;
 }
 
-int pda_ema_chunk() { return EMA_CHUNK; }
+int pda_ema_chunk() { return FLAT_CHUNK; }
 
 int pda_ema(const EmaRange* rows, int nrows, int mode, float w, int dt, hipStream_t st) {
   const int rc = pda_ema_check(rows, nrows, mode, w, dt);
@@ -163,7 +157,7 @@ int pda_ema(const EmaRange* rows, int nrows, int mode, float w, int dt, hipStrea
     const EmaRange& r = rows[i];
     if (r.count == 0) continue;
     t.rows[t.nrows++] = EmaRow{(uint32_t*)r.e, (uint32_t*)r.p, (u16*)r.shadow, r.count, blocks};
-    blocks += (r.count + EMA_CHUNK - 1) / EMA_CHUNK;
+    blocks += (r.count + FLAT_CHUNK - 1) / FLAT_CHUNK;
     if (t.nrows == EMA_MAX_ROWS) {
       const int e = flush();
       if (e) return e;

@@ -6,34 +6,29 @@
 //                 double, as the crop draw of augment.hip, and this file is compiled without FMA
 //                 contraction for the same reason: the integers must be those of a float64 Python
 //                 evaluation of the same expressions (erase.py draw_erase, tests/erase_refs.py).
-//                 The uniforms are counter-based on a stream of their own:
+//                 The uniforms are counter-based (batch_image.h) on a stream of their own:
 //                   bkey = hash32(hash32(hash32(hash32(seed*97 + 0x455241) ^ rank) ^ epoch) ^ step)  (host)
-//                   skey = hash32(bkey ^ (b*0x9E3779B9 + 0x85EBCA6B)),  b = position in the batch
-//                   u(k) = hash32(skey ^ (k+1)*0x27D4EB2F) / 2^32
+//                   skey = counter_subkey(bkey, b),  b = position in the batch
+//                   u(k) = counter_u01(skey, k)
 //                 u(0) is the gate (erase if u(0) < p); attempt a = 0..9 draws area 1+4a, log-ratio
 //                 2+4a, row 3+4a, column 4+4a and is accepted when h < S and w < S (strict, as
 //                 torchvision). Ten refusals leave the image alone.
 //   batch_erase : in place, pixels inside a sample's box become +0.0 in all three channels. The
 //                 table is device-produced, so each box is clamped to [0, S] here and an empty one
 //                 skipped. Layouts as batch_mix: the stem's 2x2 space-to-depth [B, S/2, S/2, 16]
-//                 (f32 / bf16 / f16; slot 6p + 3q + c = pixel (2i+p, 2j+q, c), slots 12..15 padding)
-//                 and NCHW f32. Only the boxes are visited: a lane owns one 16-B chunk that touches
+//                 (f32 / bf16 / f16; batch_image.h) and NCHW f32. Only the boxes are visited: a lane owns one 16-B chunk that touches
 //                 the box, stores it whole when every element of it lies inside, and otherwise
 //                 stores the inside elements one by one. Nothing is loaded, so nothing outside the
 //                 box (pixels, padding slots, the memory around the tensor) can change a bit; no LDS,
 //                 no atomics.
 #include <cmath>
 
-#include "common.h"
+#include "batch_image.h"
 #include "pda_api.h"
 
 namespace {
 
 constexpr int NT = 256;
-
-__device__ __forceinline__ double erase_u(uint32_t skey, uint32_t k) {
-  return (double)hash32(skey ^ ((k + 1u) * 0x27D4EB2Fu)) * (1.0 / 4294967296.0);   // exact in double
-}
 
 struct EraseDraw {
   uint32_t bkey;
@@ -44,19 +39,19 @@ struct EraseDraw {
 __global__ __launch_bounds__(NT) void erase_draw_kernel(int B, EraseDraw d, int* __restrict__ boxes) {
   const int b = blockIdx.x * NT + threadIdx.x;
   if (b >= B) return;
-  const uint32_t skey = hash32(d.bkey ^ ((uint32_t)b * 0x9E3779B9u + 0x85EBCA6Bu));
+  const uint32_t skey = counter_subkey(d.bkey, (uint32_t)b);
   int y1 = 0, y2 = 0, x1 = 0, x2 = 0;
-  if (erase_u(skey, 0) < d.p) {
+  if (counter_u01(skey, 0) < d.p) {
     const double S = (double)d.S, full = S * S;
     for (uint32_t a = 0; a < 10; ++a) {
-      const double area = full * (d.s0 + (d.s1 - d.s0) * erase_u(skey, 1 + 4 * a));
-      const double ar = exp(d.l0 + (d.l1 - d.l0) * erase_u(skey, 2 + 4 * a));
+      const double area = full * (d.s0 + (d.s1 - d.s0) * counter_u01(skey, 1 + 4 * a));
+      const double ar = exp(d.l0 + (d.l1 - d.l0) * counter_u01(skey, 2 + 4 * a));
       const double fh = rint(sqrt(area * ar)), fw = rint(sqrt(area / ar));
       // compared as doubles: a NaN or a side beyond int range is a refusal, never a conversion
       if (fh < S && fw < S) {
         const int h = (int)fh, w = (int)fw;
-        const int i = (int)(erase_u(skey, 3 + 4 * a) * (double)(d.S - h + 1));
-        const int j = (int)(erase_u(skey, 4 + 4 * a) * (double)(d.S - w + 1));
+        const int i = (int)(counter_u01(skey, 3 + 4 * a) * (double)(d.S - h + 1));
+        const int j = (int)(counter_u01(skey, 4 + 4 * a) * (double)(d.S - w + 1));
         y1 = i;
         y2 = i + h;
         x1 = j;
@@ -71,12 +66,8 @@ __global__ __launch_bounds__(NT) void erase_draw_kernel(int B, EraseDraw d, int*
   boxes[b * 4 + 3] = x2;
 }
 
-struct EraseBox {
-  int y1, y2, x1, x2;
-};
-
 // row b of the table, clamped to [0, S]; false: nothing to erase
-__device__ __forceinline__ bool erase_box(const int* __restrict__ boxes, int b, int S, EraseBox& bx) {
+__device__ __forceinline__ bool erase_box(const int* __restrict__ boxes, int b, int S, PixBox& bx) {
   const int* r = boxes + (size_t)b * 4;
   bx.y1 = r[0] < 0 ? 0 : r[0];
   bx.y2 = r[1] > S ? S : r[1];
@@ -91,27 +82,21 @@ __device__ __forceinline__ bool erase_box(const int* __restrict__ boxes, int b, 
 template <int EPC>
 __global__ __launch_bounds__(NT) void erase_s2d_kernel(i32x4* __restrict__ x,
                                                        const int* __restrict__ boxes, int B, int S2) {
-  constexpr int CPG = 16 / EPC;                 // chunks per pixel group
-  constexpr uint32_t FULL = (1u << EPC) - 1;
+  constexpr int CPG = S2D_CPG<EPC>;
+  constexpr uint32_t FULL = S2D_FULL<EPC>;
   const size_t cpi = (size_t)S2 * S2 * CPG;     // chunks per sample
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    EraseBox bx;
+    PixBox bx;
     if (!erase_box(boxes, b, 2 * S2, bx)) continue;
     const int i0 = bx.y1 >> 1, j0 = bx.x1 >> 1;
     const uint32_t ni = (uint32_t)(((bx.y2 - 1) >> 1) - i0 + 1), nj = (uint32_t)(((bx.x2 - 1) >> 1) - j0 + 1);
-    const uint32_t items = ni * nj * CPG;       // S <= 32768: <= 2^30
+    const uint32_t items = ni * nj * CPG;       // S2D_MAX_SIDE: <= 2^30
     i32x4* xs = x + (size_t)b * cpi;
     for (uint32_t t = blockIdx.x * NT + threadIdx.x; t < items; t += gridDim.x * NT) {
       const uint32_t g = t / CPG, ci = t % CPG;
       const uint32_t r = g / nj;
       const int oi = i0 + (int)r, oj = j0 + (int)(g - r * nj);
-      uint32_t slots = 0;                       // 12 bits: slot k inside the box
-#pragma unroll
-      for (int pq = 0; pq < 4; ++pq) {
-        const int yy = 2 * oi + (pq >> 1), xx = 2 * oj + (pq & 1);
-        if (yy >= bx.y1 && yy < bx.y2 && xx >= bx.x1 && xx < bx.x2) slots |= 7u << (3 * pq);
-      }
-      const uint32_t em = (slots >> (ci * EPC)) & FULL;
+      const uint32_t em = s2d_box_mask<EPC>(oi, oj, ci, bx);
       if (em == 0) continue;                    // (the f32 padding chunk among them)
       i32x4* c = xs + ((size_t)oi * S2 + oj) * CPG + ci;
       if (em == FULL) {
@@ -140,11 +125,11 @@ __global__ __launch_bounds__(NT) void erase_nchw_kernel(float* __restrict__ x,
                                                         const int* __restrict__ boxes, int B, int S) {
   const size_t epi = (size_t)3 * S * S;         // elements per sample
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    EraseBox bx;
+    PixBox bx;
     if (!erase_box(boxes, b, S, bx)) continue;
     const uint32_t h = (uint32_t)(bx.y2 - bx.y1), w = (uint32_t)(bx.x2 - bx.x1);
     const uint32_t ncm = (w + 3) / 4 + 1;       // most chunks a span of w floats can touch
-    const uint32_t items = 3u * h * ncm;        // S <= 26000: < 2^32
+    const uint32_t items = 3u * h * ncm;        // NCHW_MAX_SIDE: < 2^32
     for (uint32_t t = blockIdx.x * NT + threadIdx.x; t < items; t += gridDim.x * NT) {
       const uint32_t r = t / ncm, k = t - r * ncm;
       const uint32_t c = r / h;
@@ -169,7 +154,7 @@ extern "C" {
 
 int pda_erase_draw(int B, int S, unsigned bkey, double p, double s0, double s1, double l0, double l1,
                    int* boxes, hipStream_t st) {
-  if (B <= 0 || S <= 0 || S > 32768 || boxes == nullptr) return -2;
+  if (B <= 0 || S <= 0 || S > S2D_MAX_SIDE || boxes == nullptr) return -2;
   if (!(p >= 0.0 && p <= 1.0)) return -2;                     // (NaN fails both)
   if (!std::isfinite(s0) || !std::isfinite(s1) || !std::isfinite(l0) || !std::isfinite(l1)) return -2;
   if (s0 < 0.0 || s0 > s1 || l0 > l1) return -2;
@@ -188,22 +173,13 @@ int pda_erase_draw(int B, int S, unsigned bkey, double p, double s0, double s1, 
 
 int pda_batch_erase(void* x, const int* boxes, int B, int S, int dt, int layout, int grid_cap,
                     hipStream_t st) {
-  if (B <= 0 || S <= 0 || S > 32768 || x == nullptr || boxes == nullptr || grid_cap < 0) return -2;
-  if ((uintptr_t)x % 16 || (uintptr_t)boxes % 4) return -2;
+  if (!batch_args_ok(B, S, dt, layout, {x}) || grid_cap < 0) return -2;
+  if (boxes == nullptr || (uintptr_t)boxes % 4) return -2;
   // the host does not know the boxes: grid.y walks the samples, grid.x is sized for a box of a
   // third of the image (RandomErasing's largest scale), at least ~4096 blocks in all when the
   // images are that large; larger boxes take more trips of the stride loop
-  const int blocks = grid_cap > 0 && grid_cap < 65536 ? grid_cap : 65536;
-  const int gy = B < blocks ? (B < 65535 ? B : 65535) : (blocks < 65535 ? blocks : 65535);
-  auto grid = [&](long long items) {
-    long long gx = (items / 3 + NT - 1) / NT, cap = blocks / gy, want = 4096 / gy;
-    if (want < 8) want = 8;
-    if (cap > want) cap = want;
-    if (cap < 1) cap = 1;
-    return dim3((unsigned)(gx < 1 ? 1 : (gx > cap ? cap : gx)), (unsigned)gy);
-  };
+  auto grid = [&](long long items) { return batch_grid(B, items / 3, grid_cap, NT, 4096); };
   if (layout == 0) {
-    if (S % 2 || (dt != DT_F32 && dt != DT_BF16 && dt != DT_F16)) return -2;
     const int S2 = S / 2;
     const long long cpi = (long long)S2 * S2 * (dt == DT_F32 ? 4 : 2);
     i32x4* xi = (i32x4*)x;
@@ -211,12 +187,9 @@ int pda_batch_erase(void* x, const int* boxes, int B, int S, int dt, int layout,
       TRACKED_LAUNCH(erase_s2d_kernel<4>, grid(cpi), dim3(NT), 0, st, xi, boxes, B, S2);
     else
       TRACKED_LAUNCH(erase_s2d_kernel<8>, grid(cpi), dim3(NT), 0, st, xi, boxes, B, S2);
-  } else if (layout == 1) {
-    if (dt != DT_F32 || S > 26000) return -2;     // 3*S*S < 2^31
+  } else {
     TRACKED_LAUNCH(erase_nchw_kernel, grid(3LL * S * ((S + 3) / 4)), dim3(NT), 0, st, (float*)x, boxes,
                    B, S);
-  } else {
-    return -2;
   }
   return (int)hipGetLastError();
 }

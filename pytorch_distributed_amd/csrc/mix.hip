@@ -11,7 +11,7 @@
 //                (f32 / bf16 / f16, misc.hip) and NCHW f32 [B, 3, S, S]. 16 B per lane, no LDS,
 //                no atomics; a lane whose chunk lies wholly on one side of the box loads only
 //                that side.
-#include "common.h"
+#include "batch_image.h"
 #include "pda_api.h"
 
 namespace {
@@ -62,10 +62,6 @@ __global__ __launch_bounds__(NT) void xent_soft_kernel(
 }
 
 // ------------------------------------------------------------------ batch mixing
-struct MixBox {
-  int y1, y2, x1, x2;
-};
-
 // 16 B of any dtype as f32 (4 or 8 elements), mixed, rounded once
 template <int DT> __device__ __forceinline__ i32x4 mix16(i32x4 a, i32x4 b, float lam, float oml) {
   if constexpr (DT == DT_F32) {
@@ -113,17 +109,16 @@ __device__ __forceinline__ i32x4 mix_chunk(const i32x4* pa, const i32x4* pb, int
   return select16<DT>(*pa, *pb, em);
 }
 
-// s2d [B, S2, S2, 16]: grid.y walks the samples, grid.x strides over one sample's 16-B chunks
-// (CPG per 16-slot pixel group). Slot (p*2+q)*3+c = pixel (2i+p, 2j+q), slots 12..15 padding (0 in
-// both sources by the layout's contract; they follow the chunk's source like any other slot).
+// s2d [B, S2, S2, 16] (batch_image.h): grid.y walks the samples, grid.x strides over one sample's
+// 16-B chunks. The padding slots follow the chunk's source like any other slot.
 template <int DT>
 __global__ __launch_bounds__(NT) void mix_s2d_kernel(const i32x4* __restrict__ x,
                                                      i32x4* __restrict__ out, int B, int S2, int mode,
-                                                     float lam, float oml, MixBox bx) {
+                                                     float lam, float oml, PixBox bx) {
   constexpr int EPC = DT == DT_F32 ? 4 : 8;     // elements per chunk
-  constexpr int CPG = 16 / EPC;                 // chunks per pixel group
-  constexpr uint32_t FULL = (1u << EPC) - 1;
-  const uint32_t cpi = (uint32_t)S2 * S2 * CPG;   // chunks per sample (S <= 32768: < 2^31)
+  constexpr int CPG = S2D_CPG<EPC>;
+  constexpr uint32_t FULL = S2D_FULL<EPC>;
+  const uint32_t cpi = (uint32_t)S2 * S2 * CPG;   // chunks per sample (S2D_MAX_SIDE: < 2^31)
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
     const int pb = b == 0 ? B - 1 : b - 1;
     const i32x4* xa = x + (size_t)b * cpi;
@@ -134,13 +129,7 @@ __global__ __launch_bounds__(NT) void mix_s2d_kernel(const i32x4* __restrict__ x
       if (mode == 1) {
         const uint32_t g = i / CPG, ci = i % CPG;
         const int oi = (int)(g / (uint32_t)S2), oj = (int)(g - (uint32_t)oi * S2);
-        uint32_t slots = 0;                     // 12 bits: slot k inside the box
-#pragma unroll
-        for (int pq = 0; pq < 4; ++pq) {
-          const int yy = 2 * oi + (pq >> 1), xx = 2 * oj + (pq & 1);
-          if (yy >= bx.y1 && yy < bx.y2 && xx >= bx.x1 && xx < bx.x2) slots |= 7u << (3 * pq);
-        }
-        em = (slots >> (ci * EPC)) & FULL;
+        em = s2d_box_mask<EPC>(oi, oj, ci, bx);
         // a chunk whose pixels all lie in the box comes whole from the partner, padding included
         if (em == ((0x0FFFu >> (ci * EPC)) & FULL) && em != 0) em = FULL;
       }
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(NT) void mix_s2d_kernel(const i32x4* __restrict__ x
 // NCHW f32 [B, 3, S, S] with S % 4 == 0: a chunk = 4 pixels of one row
 __global__ __launch_bounds__(NT) void mix_nchw_vec_kernel(const i32x4* __restrict__ x,
                                                           i32x4* __restrict__ out, int B, int S,
-                                                          int mode, float lam, float oml, MixBox bx) {
+                                                          int mode, float lam, float oml, PixBox bx) {
   const uint32_t cpr = (uint32_t)S / 4;            // chunks per row
   const uint32_t cpi = 3u * S * cpr;               // chunks per sample
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
@@ -180,7 +169,7 @@ __global__ __launch_bounds__(NT) void mix_nchw_vec_kernel(const i32x4* __restric
 __global__ __launch_bounds__(NT) void mix_nchw_scalar_kernel(const float* __restrict__ x,
                                                              float* __restrict__ out, int B, int S,
                                                              int mode, float lam, float oml,
-                                                             MixBox bx) {
+                                                             PixBox bx) {
   const uint32_t epi = 3u * S * S;                 // elements per sample (launcher: < 2^31)
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
     const int pb = b == 0 ? B - 1 : b - 1;
@@ -216,21 +205,12 @@ int pda_xent_soft(const float* logits, int B, int K, int ld_in, const long long*
 
 int pda_batch_mix(const void* x, void* out, int B, int S, int dt, int layout, int mode, float lam,
                   float oml, int y1, int y2, int x1, int x2, int grid_cap, hipStream_t st) {
-  if (B < 1 || S < 1 || S > 32768 || x == out || x == nullptr || out == nullptr) return -2;
+  if (!batch_args_ok(B, S, dt, layout, {x, out}) || x == out || grid_cap < 0) return -2;
   if (mode != 0 && mode != 1) return -2;
   if (mode == 1 && !(0 <= y1 && y1 <= y2 && y2 <= S && 0 <= x1 && x1 <= x2 && x2 <= S)) return -2;
-  if (grid_cap < 0) return -2;
-  const MixBox bx{y1, y2, x1, x2};
-  const int blocks = grid_cap > 0 && grid_cap < 65536 ? grid_cap : 65536;
-  const int gy = B < blocks ? (B < 65535 ? B : 65535) : (blocks < 65535 ? blocks : 65535);
-  auto grid = [&](long long items) {
-    long long gx = (items + NT - 1) / NT, cap = blocks / gy;
-    if (cap < 1) cap = 1;
-    return dim3((unsigned)(gx < 1 ? 1 : (gx > cap ? cap : gx)), (unsigned)gy);
-  };
-  if ((uintptr_t)x % 16 || (uintptr_t)out % 16) return -2;
+  const PixBox bx{y1, y2, x1, x2};
+  auto grid = [&](long long items) { return batch_grid(B, items, grid_cap, NT); };
   if (layout == 0) {
-    if (S % 2 || (dt != DT_F32 && dt != DT_BF16 && dt != DT_F16)) return -2;
     const int S2 = S / 2;
     const long long cpi = (long long)S2 * S2 * (dt == DT_F32 ? 4 : 2);
     const i32x4* xi = (const i32x4*)x;
@@ -241,16 +221,13 @@ int pda_batch_mix(const void* x, void* out, int B, int S, int dt, int layout, in
       TRACKED_LAUNCH(mix_s2d_kernel<DT_BF16>, grid(cpi), dim3(NT), 0, st, xi, oi, B, S2, mode, lam, oml, bx);
     else
       TRACKED_LAUNCH(mix_s2d_kernel<DT_F16>, grid(cpi), dim3(NT), 0, st, xi, oi, B, S2, mode, lam, oml, bx);
-  } else if (layout == 1) {
-    if (dt != DT_F32 || S > 26000) return -2;     // 3*S*S < 2^31
+  } else {
     if (S % 4 == 0)
       TRACKED_LAUNCH(mix_nchw_vec_kernel, grid(3LL * S * (S / 4)), dim3(NT), 0, st, (const i32x4*)x,
                      (i32x4*)out, B, S, mode, lam, oml, bx);
     else
       TRACKED_LAUNCH(mix_nchw_scalar_kernel, grid(3LL * S * S), dim3(NT), 0, st, (const float*)x,
                      (float*)out, B, S, mode, lam, oml, bx);
-  } else {
-    return -2;
   }
   return (int)hipGetLastError();
 }

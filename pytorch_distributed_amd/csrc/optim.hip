@@ -4,9 +4,9 @@
 // buffer; its learning rate, momentum, weight decay, Nesterov bit and LARS trust coefficient live in
 // one row of a device table (SegRow), so parameter groups, frozen tensors (no row) and schedulers
 // (a re-uploaded table) need no kernel arguments. A host-built block table (BlkRow) gives every
-// workgroup one chunk of at most SEG_CHUNK elements of one segment.
+// workgroup one chunk of at most FLAT_CHUNK (common.h) elements of one segment.
 //
-//   seg_norms : per chunk, sum p^2 and sum g^2 in double, fixed-order block reduction, two doubles
+//   seg_norms : per chunk, sum p^2 and sum g^2 in double, block_sum_f64 (common.h), two doubles
 //               per block into a slab (launched only when some segment has a trust coefficient)
 //   sgd_seg   : q = LARS trust ratio from the segment's slab entries summed in ascending block
 //               order (1 without LARS); d = q (g inv + wd p); b = mom b + d; p -= lr (b | d + mom b);
@@ -23,13 +23,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int SEG_CHUNK = 4096;   // elements per block (ops/native_ops.py SEG_CHUNK)
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(NT) void seg_norms_kernel(const float* __restrict__ p,
                                                        const float* __restrict__ g,
@@ -56,20 +49,8 @@ __global__ __launch_bounds__(NT) void seg_norms_kernel(const float* __restrict__
     sg += (double)g[i] * (double)g[i];
   }
   __shared__ double red[2][NT / 64];
-  sp = wave_sum_f64(sp);
-  sg = wave_sum_f64(sg);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = sp;
-    red[1][threadIdx.x >> 6] = sg;
-  }
-  __syncthreads();
+  const double tp = block_sum_f64<NT>(sp, red[0]), tg = block_sum_f64<NT>(sg, red[1]);
   if (threadIdx.x == 0) {
-    double tp = 0.0, tg = 0.0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-      tp += red[0][w];
-      tg += red[1][w];
-    }
     slab[2 * (size_t)blockIdx.x] = tp;
     slab[2 * (size_t)blockIdx.x + 1] = tg;
   }
@@ -136,7 +117,7 @@ __global__ __launch_bounds__(NT) void sgd_seg_kernel(float* __restrict__ p, cons
     if (flags & 2) {
       u16 h[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) h[e] = dt == DT_BF16 ? f32_to_bf16(pv[e]) : f32_to_f16(pv[e]);
+      for (int e = 0; e < 4; ++e) h[e] = cvt16_rt(pv[e], dt);
       reinterpret_cast<uint2*>(shadow + b.first)[i] = *reinterpret_cast<uint2*>(h);
     }
   }
@@ -146,7 +127,7 @@ __global__ __launch_bounds__(NT) void sgd_seg_kernel(float* __restrict__ p, cons
     const float pn = sgd_elem(p[i], g[i], be, inv, q, s.lr, s.momentum, s.wd, init, nesterov);
     p[i] = pn;
     buf[i] = be;
-    if (flags & 2) shadow[i] = dt == DT_BF16 ? f32_to_bf16(pn) : f32_to_f16(pn);
+    if (flags & 2) shadow[i] = cvt16_rt(pn, dt);
   }
 }
 
@@ -172,7 +153,7 @@ int pda_seg_check(const SegRow* segs, int nseg, const BlkRow* blks, int nblk, lo
     long long at = s.off;
     for (int k = 0; k < s.nblk; ++k) {
       const BlkRow& b = blks[s.blk0 + k];
-      if (b.seg != i || b.first != at || b.count <= 0 || b.count > SEG_CHUNK) return -6;
+      if (b.seg != i || b.first != at || b.count <= 0 || b.count > FLAT_CHUNK) return -6;
       if (k + 1 < s.nblk && (b.count & 3)) return -6;   // only a segment's last chunk is ragged
       at += b.count;
     }
@@ -186,7 +167,7 @@ int pda_seg_check(const SegRow* segs, int nseg, const BlkRow* blks, int nblk, lo
   return 0;
 }
 
-int pda_seg_chunk() { return SEG_CHUNK; }
+int pda_seg_chunk() { return FLAT_CHUNK; }
 
 int pda_seg_norms(const float* p, const float* g, long long n, const void* seg_dev, const void* blk_dev,
                   const void* seg_host, const void* blk_host, int nseg, int nblk, double* slab,

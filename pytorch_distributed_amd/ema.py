@@ -187,10 +187,9 @@ def build_ema(cfg, model, ctx):
         return None
     if cfg.graph and ctx.engine == "native":
         raise ValueError(EMA_REFUSAL.format(what="MX_GRAPH=1"))
-    if getattr(model, "replicas", None) or (getattr(model, "force_replay", False)
-                                            and getattr(model, "_native", False)):
-        raise ValueError(EMA_REFUSAL.format(
-            what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+    from .runtime.graphs import DP_REPLAY, replays_captured_steps
+    if replays_captured_steps(model):
+        raise ValueError(EMA_REFUSAL.format(what=DP_REPLAY))
     inner = getattr(model, "module", model)
     cls = NativeEMA if hasattr(inner, "flat_params") else ModelEMA
     return cls(inner, cfg.ema, every=cfg.ema_every, warmup=cfg.ema_warmup)

@@ -22,8 +22,6 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .mix import _layout_of
-
 __all__ = ["batch_key", "draw_erase", "erase_torch", "BatchEraser", "SCALE", "RATIO", "ATTEMPTS"]
 
 SCALE, RATIO = (0.02, 0.33), (0.3, 3.3)     # torchvision's defaults (ops.native_ops ERASE_SCALE / ERASE_RATIO)
@@ -147,17 +145,17 @@ class BatchEraser:
         return t
 
     def __call__(self, samples: torch.Tensor, epoch: int, step: int) -> torch.Tensor:
-        layout = _layout_of(samples)
-        if layout is None:
+        from .ops import native_ops as K
+        found = K.batch_layout(samples)
+        if found is None:
             raise ValueError(f"BatchEraser: batch {tuple(samples.shape)} is neither s2d "
                              f"[B, S/2, S/2, 16] nor NCHW [B, 3, S, S]")
-        S = samples.shape[2] * (2 if layout == 0 else 1)
+        layout, S = found
         if S != self.S:
             raise ValueError(f"BatchEraser: batch of {S}x{S} images, draws made for {self.S}x{self.S}")
         samples = samples.contiguous()      # (a no-op on every loader's batch: erased in place)
         B = samples.shape[0]
         if samples.is_cuda and self.native and (layout == 0 or samples.dtype == torch.float32):
-            from .ops import native_ops as K
             table = self._table(samples)
             K.erase_draw(table, S, batch_key(self.seed, self.rank, epoch, step), self.p, self.scale,
                          self.ratio)

@@ -60,15 +60,6 @@ def draw_mix(seed: int, rank: int, epoch: int, step: int, S: int, mixup_alpha: f
     return CUTMIX, lam, (y1, y2, x1, x2)
 
 
-def _layout_of(x: torch.Tensor) -> Optional[int]:
-    """0 (s2d [B, S/2, S/2, 16]) / 1 (NCHW [B, 3, S, S]) / None."""
-    if x.dim() == 4 and x.shape[3] == 16 and x.shape[1] == x.shape[2]:
-        return 0
-    if x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3]:
-        return 1
-    return None
-
-
 def mix_torch(x: torch.Tensor, out: torch.Tensor, layout: int, mode: int, lam: float, box) -> None:
     """``batch_mix`` in plain torch (CPU, torch engine): roll by one sample, then the kernel's
     ``lam*x + (1-lam)*partner`` in f32 with the same float32 weights, rounded once (mixup), or a
@@ -116,17 +107,17 @@ class BatchMixer:
         mode, lam, box = draw_mix(self.seed, self.rank, epoch, step, self.S, self.mixup, self.cutmix)
         if mode is None:
             return samples, labels, None, 1.0
-        layout = self.layout if self.layout is not None else _layout_of(samples)
-        if layout is None or layout != _layout_of(samples):
+        from .ops import native_ops as K
+        found = K.batch_layout(samples)
+        if found is None or self.layout not in (None, found[0]):
             raise ValueError(f"BatchMixer: batch {tuple(samples.shape)} is neither s2d "
                              f"[B, S/2, S/2, 16] nor NCHW [B, 3, S, S]")
-        S = samples.shape[2] * (2 if layout == 0 else 1)
+        layout, S = found
         if S != self.S:
             raise ValueError(f"BatchMixer: batch of {S}x{S} images, draws made for {self.S}x{self.S}")
         samples = samples.contiguous()
         out = self._buffer(samples)
         if samples.is_cuda and self.native and (layout == 0 or samples.dtype == torch.float32):
-            from .ops import native_ops as K
             K.batch_mix(samples, out, layout, mode, lam, box)
         else:
             mix_torch(samples, out, layout, mode, lam, box)

@@ -29,8 +29,8 @@ __all__ = [
     "bn_apply", "stem_pool", "maxpool_bwd", "tail_pool", "bn_epilogue", "bn_bwd_finish",
     "bn_bwd", "xent", "topk_hits", "col_sum", "sgd_flat", "cast_flat", "amp_scan",
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
-    "aug_draw", "aug_resize_dev", "aug_record_bytes",
-    "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg", "grad_clip",
+    "aug_draw", "aug_resize_dev", "aug_record_bytes", "batch_layout", "batch_shape",
+    "FLAT_CHUNK", "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg", "grad_clip",
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
     "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
 ]
@@ -1292,7 +1292,8 @@ def amp_scan(g, found_inf, inv_scale, scale, tracker, ws, growth=2.0, backoff=0.
 
 
 # ------------------------------------------------------------------ segmented optimizer (csrc/optim.hip)
-SEG_CHUNK = 4096      # elements one block of seg_norms / sgd_seg handles (csrc/optim.hip SEG_CHUNK)
+FLAT_CHUNK = 4096     # most elements one block of a flat-buffer kernel handles (csrc/common.h)
+SEG_CHUNK = FLAT_CHUNK    # seg_norms / sgd_seg / grad_clip block rows
 SEG_NESTEROV = 1      # SegRow.flags
 
 
@@ -1466,7 +1467,7 @@ def grad_clip(g, tables: SegTables, max_norm: float, slab, cnt, out, inv_scale=N
 
 
 # ------------------------------------------------------------------ weight EMA (csrc/ema.hip)
-EMA_CHUNK = 4096                          # elements one block of the EMA kernel handles
+EMA_CHUNK = FLAT_CHUNK                    # elements one block of the EMA kernel handles
 EMA_LERP, EMA_COPY, EMA_SWAP = 0, 1, 2    # csrc/ema.hip EmaMode
 
 
@@ -1575,7 +1576,53 @@ def nchw_to_s2d(x, out) -> None:
 # ------------------------------------------------------------------ folder-image augmentation
 AUG_S2D, AUG_NCHW = 0, 1
 AUG_RGB, AUG_YUV420 = 0, 1          # source record format: HWC RGB | Y plane + half-resolution CbCr
-AUG_MAX_SIDE = 32768
+AUG_MAX_SIDE = 32768               # csrc/batch_image.h S2D_MAX_SIDE
+NCHW_MAX_SIDE = 26000              # ... NCHW_MAX_SIDE: 3*S*S < 2^31
+
+
+def batch_layout(x) -> Optional[Tuple[int, int]]:
+    """``(layout, S)`` of a model-ready batch: ``AUG_S2D`` [B, S/2, S/2, 16] or ``AUG_NCHW``
+    [B, 3, S, S]; None for any other shape (no shape fits both)."""
+    if x.dim() == 4 and x.shape[3] == 16 and x.shape[1] == x.shape[2]:
+        return AUG_S2D, 2 * x.shape[1]
+    if x.dim() == 4 and x.shape[1] == 3 and x.shape[2] == x.shape[3]:
+        return AUG_NCHW, x.shape[2]
+    return None
+
+
+_BATCH_SAYS = {"s2d": "s2d input must be [B, S/2, S/2, 16], got {shape}", "dtype": "unsupported dtype {dtype}",
+               "nchw": "NCHW input must be [B, 3, S, S], got {shape}", "f32": "the NCHW layout is f32, got {dtype}",
+               "even": "the image side must be even, got {S}", "contiguous": "x must be contiguous",
+               "side": "empty batch or image side {S} out of range"}
+
+
+def batch_shape(what: str, t, layout: int, B: Optional[int] = None, smin: int = 1, capped: bool = True,
+                even: bool = False, contiguous: bool = True, says=None) -> Tuple[int, int]:
+    """``(B, S)`` of the model-ready batch ``t`` in ``layout``, or ``ValueError("{what}: ...")``: shape
+    (of ``B`` rows, when given), dtype, an ``even`` side, ``smin <= S`` (``capped``: <= the kernels'
+    ``AUG_MAX_SIDE`` / ``NCHW_MAX_SIDE``), contiguity. ``says`` rewords refusals: a dict over the keys
+    of ``_BATCH_SAYS``, or one string for all but the layout's. Pure Python: no library is loaded."""
+    if layout not in (AUG_S2D, AUG_NCHW):
+        raise ValueError(f"{what}: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
+    found = batch_layout(t)
+    S = found[1] if found else 0
+
+    def refuse(key):
+        text = says if isinstance(says, str) else {**_BATCH_SAYS, **(says or {})}[key]
+        raise ValueError(f"{what}: " + text.format(shape=tuple(t.shape), dtype=t.dtype, S=S))
+
+    s2d = layout == AUG_S2D
+    if found is None or found[0] != layout or (B is not None and t.shape[0] != B):
+        refuse("s2d" if s2d else "nchw")
+    if t.dtype not in ext.DT if s2d else t.dtype != torch.float32:
+        refuse("dtype" if s2d else "f32")
+    if even and S % 2:
+        refuse("even")
+    if t.shape[0] < 1 or S < smin or (capped and S > (AUG_MAX_SIDE if s2d else NCHW_MAX_SIDE)):
+        refuse("side")
+    if contiguous and not t.is_contiguous():
+        refuse("contiguous")
+    return t.shape[0], S
 
 
 def aug_record_bytes(H: int, W: int, fmt: int) -> int:
@@ -1604,24 +1651,13 @@ def aug_check(packed, table_i64, table_f64, out, layout: int, fmt: int = AUG_RGB
     B = table_i64.shape[0]
     if B < 1 or table_f64.shape[0] != B:
         raise ValueError("aug_resize: the tables must have the same B >= 1 rows")
-    if layout == AUG_S2D:
-        if out.dim() != 4 or out.shape[0] != B or out.shape[1] != out.shape[2] or out.shape[3] != 16:
-            raise ValueError(f"aug_resize: s2d output must be [{B}, S/2, S/2, 16], got {tuple(out.shape)}")
-        if out.dtype not in ext.DT:
-            raise ValueError(f"aug_resize: unsupported output dtype {out.dtype}")
-        S = 2 * out.shape[1]
-    elif layout == AUG_NCHW:
-        if out.dim() != 4 or out.shape[0] != B or out.shape[1] != 3 or out.shape[2] != out.shape[3]:
-            raise ValueError(f"aug_resize: NCHW output must be [{B}, 3, S, S], got {tuple(out.shape)}")
-        if out.dtype != torch.float32:
-            raise ValueError("aug_resize: the NCHW layout is f32")
-        S = out.shape[2]
-        if S % 2:
-            raise ValueError(f"aug_resize: the output size must be even, got {S}")
-    else:
-        raise ValueError(f"aug_resize: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
-    if S < 2 or not out.is_contiguous():
-        raise ValueError("aug_resize: the output must be contiguous with S >= 2")
+    _, S = batch_shape("aug_resize", out, layout, B, smin=2, capped=False, even=True, says={
+        "s2d": f"s2d output must be [{B}, S/2, S/2, 16], got {{shape}}",
+        "nchw": f"NCHW output must be [{B}, 3, S, S], got {{shape}}",
+        "dtype": "unsupported output dtype {dtype}", "f32": "the NCHW layout is f32",
+        "even": "the output size must be even, got {S}",
+        "side": "the output must be contiguous with S >= 2",
+        "contiguous": "the output must be contiguous with S >= 2"})
     if out.device != packed.device:
         raise ValueError(f"aug_resize: output on {out.device}, packed images on {packed.device}")
     n = packed.numel()
@@ -1675,23 +1711,7 @@ def mix_weights(lam: float) -> Tuple[float, float]:
 def batch_mix_check(x, out, layout: int, mode: int, lam: float, box=None) -> Tuple[int, int, tuple]:
     """Host-side validation of a :func:`batch_mix` call; returns (B, S, box). Pure Python (the
     kernel library is not loaded), run before the launch: the kernel trusts the shape and the box."""
-    if layout == AUG_S2D:
-        if x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] != 16:
-            raise ValueError(f"batch_mix: s2d input must be [B, S/2, S/2, 16], got {tuple(x.shape)}")
-        if x.dtype not in ext.DT:
-            raise ValueError(f"batch_mix: unsupported dtype {x.dtype}")
-        S = 2 * x.shape[1]
-    elif layout == AUG_NCHW:
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-            raise ValueError(f"batch_mix: NCHW input must be [B, 3, S, S], got {tuple(x.shape)}")
-        if x.dtype != torch.float32:
-            raise ValueError(f"batch_mix: the NCHW layout is f32, got {x.dtype}")
-        S = x.shape[2]
-    else:
-        raise ValueError(f"batch_mix: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
-    B = x.shape[0]
-    if B < 1 or S < 1 or S > (AUG_MAX_SIDE if layout == AUG_S2D else 26000):
-        raise ValueError(f"batch_mix: empty batch or image side {S} out of range")
+    B, S = batch_shape("batch_mix", x, layout, contiguous=False)      # (contiguity: with out, below)
     if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
         raise ValueError(f"batch_mix: out must have the shape, dtype and device of x "
                          f"({tuple(x.shape)} {x.dtype} {x.device}), got {tuple(out.shape)} {out.dtype} "
@@ -1787,25 +1807,7 @@ def batch_erase_check(x, boxes, layout: int) -> Tuple[int, int]:
     """Host-side validation of a :func:`batch_erase` call; returns (B, S). Pure Python (the kernel
     library is not loaded), run before the launch. The table's VALUES are not read: the kernel
     clamps every box to the image."""
-    if layout == AUG_S2D:
-        if x.dim() != 4 or x.shape[1] != x.shape[2] or x.shape[3] != 16:
-            raise ValueError(f"batch_erase: s2d input must be [B, S/2, S/2, 16], got {tuple(x.shape)}")
-        if x.dtype not in ext.DT:
-            raise ValueError(f"batch_erase: unsupported dtype {x.dtype}")
-        S = 2 * x.shape[1]
-    elif layout == AUG_NCHW:
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
-            raise ValueError(f"batch_erase: NCHW input must be [B, 3, S, S], got {tuple(x.shape)}")
-        if x.dtype != torch.float32:
-            raise ValueError(f"batch_erase: the NCHW layout is f32, got {x.dtype}")
-        S = x.shape[2]
-    else:
-        raise ValueError(f"batch_erase: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
-    B = x.shape[0]
-    if B < 1 or S < 1 or S > (AUG_MAX_SIDE if layout == AUG_S2D else 26000):
-        raise ValueError(f"batch_erase: empty batch or image side {S} out of range")
-    if not x.is_contiguous():
-        raise ValueError("batch_erase: x must be contiguous")
+    B, S = batch_shape("batch_erase", x, layout)
     _erase_table_check("batch_erase", boxes, B)
     if boxes.device != x.device:
         raise ValueError(f"batch_erase: boxes on {boxes.device}, the batch on {x.device}")
@@ -1899,17 +1901,11 @@ def aug_resize_dev(packed, ti_dev, tf_dev, out, layout: int = AUG_S2D, fmt: int 
     B = ti_dev.shape[0]
     if B < 1 or tf_dev.shape[0] != B:
         raise ValueError("aug_resize_dev: the tables must have the same B >= 1 rows")
-    if layout == AUG_S2D:
-        S = 2 * out.shape[1] if out.dim() == 4 else 0
-        ok = out.dim() == 4 and tuple(out.shape) == (B, S // 2, S // 2, 16) and out.dtype in ext.DT
-    elif layout == AUG_NCHW:
-        S = out.shape[2] if out.dim() == 4 else 0
-        ok = out.dim() == 4 and tuple(out.shape) == (B, 3, S, S) and out.dtype == torch.float32
-    else:
-        raise ValueError(f"aug_resize_dev: layout must be {AUG_S2D} (s2d) or {AUG_NCHW} (NCHW f32)")
-    if not ok or S < 2 or S % 2 or not out.is_contiguous() or out.data_ptr() % 16:
-        raise ValueError(f"aug_resize_dev: output {tuple(out.shape)} {out.dtype} does not fit layout "
-                         f"{layout} for {B} images (even S >= 2, contiguous, 16-byte aligned)")
+    unfit = (f"output {{shape}} {{dtype}} does not fit layout {layout} for {B} images (even S >= 2, "
+             f"contiguous, 16-byte aligned)")
+    _, S = batch_shape("aug_resize_dev", out, layout, B, smin=2, capped=False, even=True, says=unfit)
+    if out.data_ptr() % 16:
+        raise ValueError("aug_resize_dev: " + unfit.format(shape=tuple(out.shape), dtype=out.dtype))
     mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
     check(ext.lib().pda_aug_resize_fmt(ptr(packed), ptr(ti_dev), ptr(tf_dev), B, S, ptr(out), dt_of(out),
                                        layout, fmt, mean, std, stream(out.device)), "aug_resize_dev")

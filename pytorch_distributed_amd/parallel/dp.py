@@ -172,17 +172,17 @@ class DataParallel(nn.Module):
     def _refuse_segmented(self, segmented: bool) -> None:
         """The replica-graph path (several devices, or PDA_DP_FORCE_REPLAY=1 on one) takes no
         segmented optimizer; one device runs the module's own eager step and does."""
-        if segmented and self._native and (self.replicas or self.force_replay):
-            from ..runtime.graphs import SEGMENTED_REFUSAL
-            raise ValueError(SEGMENTED_REFUSAL.format(
-                what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+        from ..runtime.graphs import DP_REPLAY, SEGMENTED_REFUSAL, replays_captured_steps
+        # (the torch engine's replicas step one torch optimizer: only the native wrapper refuses)
+        if segmented and self._native and replays_captured_steps(self):
+            raise ValueError(SEGMENTED_REFUSAL.format(what=DP_REPLAY))
 
     def _refuse_clip(self, clip: float) -> None:
-        """As :meth:`_refuse_segmented`, for gradient clipping (``clip_grad_norm > 0``)."""
-        if clip and (self.replicas or (self.force_replay and self._native)):
-            from ..runtime.graphs import CLIP_REFUSAL
-            raise ValueError(CLIP_REFUSAL.format(
-                what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+        """As :meth:`_refuse_segmented`, for gradient clipping (``clip_grad_norm > 0``); a torch
+        wrapper with replicas refuses it too."""
+        from ..runtime.graphs import CLIP_REFUSAL, DP_REPLAY, replays_captured_steps
+        if clip and replays_captured_steps(self):
+            raise ValueError(CLIP_REFUSAL.format(what=DP_REPLAY))
 
     def make_optimizer(self, **kw):
         self._refuse_clip(kw.get("clip_grad_norm", 0.0))

@@ -151,6 +151,16 @@ CLIP_REFUSAL = ("{what} cannot run MX_CLIP_GRAD_NORM: the replicated optimizers 
                 "MX_CLIP_GRAD_NORM / clip_grad_norm")
 
 
+DP_REPLAY = "DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"   # the refusals' {what}
+
+
+def replays_captured_steps(model) -> bool:
+    """True for a DataParallel wrapper that trains by replaying its replica graphs: one with
+    replicas, or a native one with ``PDA_DP_FORCE_REPLAY=1`` (``MX_GRAPH=1`` is a property of the run)."""
+    return bool(getattr(model, "replicas", None)
+                or (getattr(model, "force_replay", False) and getattr(model, "_native", False)))
+
+
 class GraphedNativeStep:
     """Capture-once / replay-per-step driver of :func:`native_train_step`.
 

@@ -401,11 +401,9 @@ def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
     native = hasattr(inner, "make_optimizer")
     clip = {}
     if cfg.clip_grad_norm > 0:
-        if getattr(model, "replicas", None) or (getattr(model, "force_replay", False)
-                                                and getattr(model, "_native", False)):
-            from .runtime.graphs import CLIP_REFUSAL
-            raise ValueError(CLIP_REFUSAL.format(
-                what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+        from .runtime.graphs import CLIP_REFUSAL, DP_REPLAY, replays_captured_steps
+        if replays_captured_steps(model):
+            raise ValueError(CLIP_REFUSAL.format(what=DP_REPLAY))
         clip = dict(clip_grad_norm=cfg.clip_grad_norm)
     if not (cfg.nesterov or cfg.no_bn_decay or cfg.lars > 0):
         if native:
@@ -434,10 +432,9 @@ def _refuse_soft_targets(cfg: RunConfig, model: nn.Module, ctx: Context) -> None
     from .mix import MIX_REFUSAL
     if cfg.graph and ctx.engine == "native":
         raise ValueError(MIX_REFUSAL.format(what="MX_GRAPH=1"))
-    if getattr(model, "replicas", None) or (getattr(model, "force_replay", False)
-                                            and getattr(model, "_native", False)):
-        raise ValueError(MIX_REFUSAL.format(
-            what="DataParallel over several devices (or with PDA_DP_FORCE_REPLAY=1)"))
+    from .runtime.graphs import DP_REPLAY, replays_captured_steps
+    if replays_captured_steps(model):
+        raise ValueError(MIX_REFUSAL.format(what=DP_REPLAY))
 
 
 def build_criterion(ctx: Context, model: nn.Module):

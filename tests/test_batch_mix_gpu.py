@@ -16,7 +16,7 @@ U24 = 2.0 ** -24
 GUARD = 64           # elements on each side of ``out`` (a multiple of 16 bytes in every dtype)
 
 CASES = ([(R.S2D, dt, S) for dt in (torch.float32, torch.bfloat16, torch.float16) for S in (4, 10, 32)]
-         + [(R.NCHW, torch.float32, S) for S in (6, 10, 32)])
+         + [(R.NCHW, torch.float32, S) for S in (4, 6, 10, 32)])   # 4: rows of 16 bytes
 IDS = [f"{'s2d' if l == R.S2D else 'nchw'}-{str(dt).split('.')[1]}-S{S}" for l, dt, S in CASES]
 
 
@@ -82,12 +82,12 @@ def _pads_zero(out, layout):
 
 @pytest.mark.parametrize("layout,dtype,S", CASES, ids=IDS)
 def test_cutmix_is_a_bit_exact_select(layout, dtype, S):
-    """B in {1, 2, 5} x seven boxes: the empty box, the whole image, one pixel at odd (y, x) (it
+    """B in {1, 2, 3, 5} x seven boxes: the empty box, the whole image, one pixel at odd (y, x) (it
     splits an s2d 2x2 group), boxes flush with row / column 0 and with S, one row, one column. The
     output bit-equals the reference (the NaN and the signed zeros travel with their pixels), the
     guard bands and the input are intact, s2d slots 12..15 stay 0."""
     K = _k()
-    for B in (1, 2, 5):
+    for B in (1, 2, 3, 5):
         x = _input(layout, dtype, S, B)
         for name, box in _boxes(S).items():
             ref = R.batch_mix_ref(x, layout, R.CUTMIX, 0.5, box)

@@ -16,7 +16,7 @@ GUARD = 64           # elements on each side of the batch (a multiple of 16 byte
 SENTINEL = 0x5A5A5A5A
 
 CASES = ([(R.S2D, dt, S) for dt in (torch.float32, torch.bfloat16, torch.float16) for S in (4, 10, 32)]
-         + [(R.NCHW, torch.float32, S) for S in (6, 10, 32)])
+         + [(R.NCHW, torch.float32, S) for S in (4, 6, 10, 32)])   # 4: rows of 16 bytes
 IDS = [f"{'s2d' if l == R.S2D else 'nchw'}-{str(dt).split('.')[1]}-S{S}" for l, dt, S in CASES]
 
 
