@@ -681,6 +681,10 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, g: ConvGeom, grad: torch.Tenso
     the plain dz^T x, and the split-K reduce writes k1*(dz^T x) + k2*B + k3*s^T per row, with
     B = W Gram(x) and s the column sums of x (:func:`conv_wgrad_gram`, :func:`fold_bgemm`)."""
     Nb = dy.shape[0]
+    if combine is not None and g.Cin & (g.Cin - 1):
+        # the reduce decodes a slab column as n >> log2(Cin): a truncated log2 would pair the rows
+        # of B and s with the wrong columns (see wgrad_tap_ok)
+        raise ValueError(f"conv_wgrad: combine needs a power-of-two Cin, got {g.Cin}")
     if (tile is None and target_blocks is None and bna is None and combine is None
             and cin_real is None and wgrad_tap_ok(g, dy.dtype)):
         return conv_wgrad_tap(dy, x, g, grad, ws, scale, accumulate, pro)
@@ -888,6 +892,8 @@ def conv_wgrad_gram(y: torch.Tensor, sc: torch.Tensor, sh: torch.Tensor, gram: t
     Nb, H, W, C_ = y.shape
     if gram.numel() < (C_ + 1) * C_ or gram.dtype != torch.float32:
         raise ValueError("conv_wgrad_gram: gram f32 [C + 1][C]")
+    if C_ & (C_ - 1):    # the reduce decodes a slab column as n >> log2(C) (see wgrad_tap_ok)
+        raise ValueError(f"conv_wgrad_gram: C = {C_} is not a power of two")
     P = Nb * H * W
     bm, bn = (64, 64) if C_ <= 64 else (-128, 128)
     tiles = math.ceil(C_ / tile_rows(bm)) * math.ceil(C_ / bn)

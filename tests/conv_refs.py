@@ -18,7 +18,11 @@ integer data of the cases, which :func:`assert_exact_conditions` proves per case
   (``pk.x = pack2<DT>(f32x2{v[0], v[1]})`` in the staging loop), i.e. dA is rounded to 16 bits
   BEFORE ``g2`` is added and the mask applied (:func:`dgrad_epi_ref` rounds it there too);
 * WGRAD_BNA rounds dY = fma(k1, dz, fma(k2, y, k3)) to 16 bits while staging
-  (``pack2<DT>(bnb_affine2(...))``).
+  (``pack2<DT>(bnb_affine2(...))``);
+* bn_fold_kernel rounds k1 o W, k2 o W and (once, at the store) G to 16 bits.
+
+The consumer-side fold's data gradient exceeds 256: it is rounded ONCE at the 16-bit C tile (after
+the f32 bias add), and the references round the exact integer there (:func:`round_to`).
 """
 import functools
 from dataclasses import dataclass
@@ -108,6 +112,43 @@ PASS_TILES = {
 }
 
 
+# the consumer-side BatchNorm-backward fold (csrc/conv_gemm.hip BNF_CASE / GRAM_CASE tables)
+BNF_TILES = [(-128, 64), (-128, 128), (64, 64), (64, 128)]
+GRAM_TILES = [(64, 64), (-128, 128), (-128, 64)]
+
+# Fold geometries: 1x1 convs without padding, Cin and Cout multiples of 64 and powers of two. D is
+# the stride-2 shortcut (only parity class (0, 0) lands), F the square one-tile case; P = Nb*H*W is
+# 105 (FA), 126 (FB), 35 (FC) and 60 (FD): ragged against 64- and 128-row tiles, below 64, and
+# several 64-row splits with a short last one; Cin = 64, 128, 256, 512; Cout above and below Cin.
+# The new ones are not in CASES: the plain passes hold their tiles on CASES already.
+FOLD_CASES = {c.id: c for c in [
+    CASES["D"], CASES["F"],
+    Case("FA", 3, 5, 7, 64, 256, 1, 1, 1, 0, passes=("dgrad", "wgrad")),
+    Case("FB", 2, 7, 9, 128, 512, 1, 1, 1, 0, passes=("dgrad", "wgrad")),
+    Case("FC", 1, 5, 7, 256, 1024, 1, 1, 1, 0, passes=("dgrad", "wgrad")),
+    Case("FD", 2, 5, 6, 512, 128, 1, 1, 1, 0, passes=("dgrad", "wgrad")),
+]}
+GRAM_CASES = [i for i in sorted(FOLD_CASES) if FOLD_CASES[i].stride == 1]   # conv3 of a tail: stride 1
+
+
+def compiled_tiles(table: str):
+    """dtype name -> [(bm, bn)] of the ``table``(DT, M, N, STAGES) entries of csrc/conv_gemm.hip, read
+    from the source text, as the tile codes the launchers take (single-stage: bm = -M)."""
+    import pathlib
+    import re
+
+    import pytorch_distributed_amd
+    text = (pathlib.Path(pytorch_distributed_amd.__file__).parent / "csrc" / "conv_gemm.hip").read_text()
+    out = {}
+    for dt, m, n, st in re.findall(r"\b%s\((DT_\w+), (\d+), (\d+), (\d+)\)" % table, text):
+        out.setdefault(dt, []).append((-int(m) if st == "1" else int(m), int(n)))
+    return out
+
+
+def _case(cid: str) -> Case:
+    return CASES[cid] if cid in CASES else FOLD_CASES[cid]
+
+
 def tile_rows(bm: int) -> int:
     return bm - 2000 if bm > 2000 else bm - 1000 if bm > 1000 else abs(bm)
 
@@ -144,6 +185,20 @@ def tail_ok(c: Case) -> bool:
 
 def accepts_bna(tile, c: Case) -> bool:
     return "wgrad" in c.passes and tile in BNA_TILES and c.rows % 8 == 0
+
+
+def accepts_bnf(tile, c: Case) -> bool:
+    """DGRAD_BNF (``pda_conv_dgrad_bnf`` and ``dgrad_params``): a 1x1 conv without padding, whole
+    64-column panels, stride 1 or a stride-2 shortcut on an even image."""
+    return (tile in BNF_TILES and c.R == 1 and c.S == 1 and c.pad == 0 and c.Cin % 64 == 0
+            and c.Cout % 64 == 0 and c.stride in (1, 2) and c.H % c.stride == 0 and c.W % c.stride == 0)
+
+
+def accepts_gram(tile, c: Case) -> bool:
+    """WGRAD_GRAM on the conv's input (C = Cin channels at stride 1); the reduce decodes a slab
+    column by a shift, so C is a power of two."""
+    return (tile in GRAM_TILES and c.R == 1 and c.S == 1 and c.pad == 0 and c.stride == 1
+            and c.Cin % 8 == 0 and _pow2(c.Cin))
 
 
 # ------------------------------------------------------------------ data
@@ -387,7 +442,7 @@ EPI_VARIANTS = [(0, False), (0, True), (1, False), (1, True), (2, False), (2, Tr
 
 @functools.lru_cache(maxsize=None)
 def epi_operands(cid: str):
-    c = CASES[cid]
+    c = _case(cid)
     shp = (c.Nb, c.H, c.W, c.Cin)
     sc, sh = coeffs(c.Cin, 31)
     sc2, sh2 = coeffs(c.Cin, 32)
@@ -437,8 +492,139 @@ def wgrad_variants(cid: str, dtype):
     return out
 
 
+# ------------------------------------------------------------------ the consumer-side BatchNorm-backward fold
+# dY = k1*dz + k2*y + k3 with y = a2 . W^T (the conv's own forward) is never materialised:
+#   dX = dY . W    = dz . (k1 o W) + a2 . G + b,   G = W^T diag(k2) W,  b = W^T k3       (DGRAD_BNF)
+#   dW = dY^T a2   = diag(k1) (dz^T a2) + diag(k2) W Gram(a2) + k3 s^T,  s = colsum(a2)  (the combine)
+# Both are identities on integers, so the references below are the UNFOLDED definition (y, dY, then
+# the plain conv backward) and the kernels must meet them bit for bit.
+FOLD_LIM = 2    # |dz|, |xa| <= 2: every fold case meets its bounds with it (check_fold_conditions)
+
+
+@functools.lru_cache(maxsize=None)
+def fold_operands(cid: str):
+    """w [Cout,Cin] in {-1,0,1}, k1 / k2 in {+-1, +-2}, k3 in {-1,0,1} (per Cout), dz [Nb,Ho,Wo,Cout],
+    xa [Nb,H,W,Cin] (the Gram operand: the conv's input as it is, or PRE-BatchNorm with the prologue
+    coefficients sc / sh). float64 integers. Cached: do not modify."""
+    c = FOLD_CASES[cid]
+    seed = 5000 + 31 * sorted(FOLD_CASES).index(cid)
+    g = _gen(seed + 3)
+
+    def pick(vals):
+        return torch.tensor(vals, dtype=F64)[torch.randint(0, len(vals), (c.Cout,), generator=g)]
+
+    sc, sh = coeffs(c.Cin, seed + 4)
+    return dict(w=ints((c.Cout, c.Cin), 1, seed), dz=ints((c.Nb, c.Ho, c.Wo, c.Cout), FOLD_LIM, seed + 1),
+                xa=ints((c.Nb, c.H, c.W, c.Cin), FOLD_LIM, seed + 2), k1=pick((1.0, 2.0, -1.0, -2.0)),
+                k2=pick((1.0, 2.0, -1.0, -2.0)), k3=torch.randint(-1, 2, (c.Cout,), generator=g).to(F64), sc=sc, sh=sh)
+
+
+@functools.lru_cache(maxsize=None)
+def fold_refs(cid: str, dtype, pro: bool):
+    """The unfolded definition in float64: a2 (= xa, or relu(xa*sc+sh) rounded as the prologue
+    does), y = conv(a2), dY = k1*dz + k2*y + k3, then dx [Nb,H,W,Cin] and dw [Cout,Cin] of the plain
+    conv backward on dY. Cached: do not modify."""
+    c = FOLD_CASES[cid]
+    o = fold_operands(cid)
+    a2 = pro_ref(o["xa"], o["sc"], o["sh"], dtype) if pro else o["xa"]
+    w4 = o["w"].reshape(c.Cout, 1, 1, c.Cin)
+    y = conv_fwd_ref(a2, w4, c)
+    dY = o["k1"] * o["dz"] + o["k2"] * y + o["k3"]
+    dx, dw = conv_bwd_ref(a2, w4, dY, c)
+    return dict(a2=a2, y=y, dY=dY, dx=dx, dw=dw.reshape(c.Cout, c.Cin))
+
+
+def bn_fold_ref(w, k1, k2, k3, dtype):
+    """bn_fold_kernel: (wf [Cout + Cin, Cin], b [Cin]) float64. Rows [0, Cout) = k1 o W rounded to 16
+    bits; G[i][j] = sum_k W[k][i] * round16(k2[k] * W[k][j]), rounded once at the store; b = W^T k3
+    stays f32."""
+    wk2 = r64(k2[:, None] * w, dtype)
+    return torch.cat([r64(k1[:, None] * w, dtype), r64(w.t() @ wk2, dtype)]), w.t() @ k3
+
+
+def assert_fold_operands_exact(name: str, w, k1, k2, k3) -> None:
+    """The bn_fold premises: k1 o W, k2 o W and the UNROUNDED G are representable in both 16-bit
+    dtypes, and G's and b's accumulations stay below 2^24."""
+    wk2 = k2[:, None] * w
+    assert_exact_conditions(name, stored16=(w, k1[:, None] * w, wk2, w.t() @ wk2),
+                            acc_abs=(w.abs().t() @ wk2.abs(), w.abs().t() @ k3.abs()))
+
+
+def dgrad_bnf_variants(cid: str, dtype, pro: bool):
+    """"plain" -> dict(dx=) the unfolded dX rounded once at the 16-bit C tile; (mode, with_g2) ->
+    dict(dz=, tot=, mask=) for the fused epilogue, which takes that rounded value as dA
+    (:func:`dgrad_epi_ref`)."""
+    dA = fold_refs(cid, dtype, pro)["dx"]
+    o = epi_operands(cid)
+    _, m1 = tail_ref(o["y"], o["sc"], o["sh"], o["y2"], dtype)
+    out = {"plain": dict(dx=r64(dA, dtype))}
+    for mode, wg in EPI_VARIANTS:
+        dz, tot = dgrad_epi_ref(dA, mode, o["y"], o["sc"], o["sh"], dtype,
+                                y2=o["y2"] if mode in (1, 2) else None,
+                                sc2=o["sc2"] if mode == 2 else None, sh2=o["sh2"] if mode == 2 else None,
+                                g2=o["g2"] if wg else None, mask=m1 if mode == 3 else None)
+        out[(mode, wg)] = dict(dz=dz, tot=tot, mask=m1 if mode == 3 else None)
+    return out
+
+
+def gram_ref(y, sc, sh, dtype):
+    """WGRAD_GRAM: (a^T a [C,C], colsum a [C]) float64 of a = round16(relu(y*sc+sh))."""
+    a = pro_ref(y, sc, sh, dtype).reshape(-1, y.shape[-1])
+    return a.t() @ a, a.sum(0)
+
+
+def fold_combine_ref(S, k1, k2, k3, B, s) -> torch.Tensor:
+    """The k-combine of the split-K reduce: row n1 of the summed slab S becomes
+    k1[n1]*S + k2[n1]*B[n1] + k3[n1]*s."""
+    return k1[:, None] * S + k2[:, None] * B + k3[:, None] * s[None, :]
+
+
+def check_fold_conditions(cid: str, dtype) -> None:
+    """:func:`assert_exact_conditions` for everything the fold tests run on this case: every 16-bit
+    operand (G included) representable, every |.|-accumulation of every GEMM below 2^24."""
+    c = FOLD_CASES[cid]
+    o = fold_operands(cid)
+    w, k1, k2, k3, dz = o["w"], o["k1"], o["k2"], o["k3"], o["dz"]
+    assert_fold_operands_exact(f"{cid}/bn_fold", w, k1, k2, k3)
+    wf, b = bn_fold_ref(w, k1, k2, k3, dtype)
+    e = epi_operands(cid)
+    ey, ey2 = e["y"].abs().reshape(-1, c.Cin), e["y2"].abs().reshape(-1, c.Cin)
+    dzr = dz.abs().reshape(-1, c.Cout)
+    for pro in (False, True):
+        r = fold_refs(cid, dtype, pro)
+        a2 = r["a2"]
+        a2s = a2[:, ::c.stride, ::c.stride].abs().reshape(-1, c.Cin)    # the pixels a tap lands on
+        assert_exact_conditions(
+            f"{cid}/dgrad_bnf/pro{int(pro)}", stored16=(dz, o["xa"], a2, e["y"], e["y2"], e["g2"]),
+            acc_abs=(dzr @ wf[:c.Cout].abs() + a2s @ wf[c.Cout:].abs() + b.abs(),))
+        g = r64(r["dx"], dtype).abs() + e["g2"].abs()     # bounds dA, dA + g2 and the stored dz
+        g = g.reshape(-1, c.Cin)
+        assert_exact_conditions(f"{cid}/dgrad_bnf/epi/pro{int(pro)}",
+                                acc_abs=(g.sum(0), (g * ey).sum(0), (g * ey2).sum(0)))
+        for key, v in dgrad_bnf_variants(cid, dtype, pro).items():
+            if key != "plain":     # what is stored is a 16-bit value by construction; sums exact in f32
+                assert float(v["tot"].abs().max()) < LIM_ACC, (cid, key)
+    if cid not in GRAM_CASES:
+        return
+    r = fold_refs(cid, dtype, True)
+    a2 = r["a2"].reshape(-1, c.Cin)
+    gram, s = gram_ref(o["xa"], o["sc"], o["sh"], dtype)
+    S = dzr.t() @ a2.abs()
+    B = w.abs() @ gram.abs()
+    assert_exact_conditions(
+        f"{cid}/wgrad_fold", stored16=(r["y"], r["dY"]),      # WGRAD_BNA reads y and rounds dY
+        acc_abs=(a2.abs().t() @ a2.abs(), a2.abs().sum(0), B, S,
+                 fold_combine_ref(S, k1.abs(), k2.abs(), k3.abs(), B, s.abs()),
+                 r["dY"].abs().reshape(-1, c.Cout).t() @ a2.abs(),
+                 1024 + r["dw"].abs()))     # scaled accumulation onto the prefill: 2 fraction bits
+
+
 def check_case_conditions(cid: str, dtype) -> None:
     """:func:`assert_exact_conditions` for every variant the GPU file runs on this case."""
+    if cid in FOLD_CASES:
+        check_fold_conditions(cid, dtype)
+    if cid not in CASES:
+        return
     c = CASES[cid]
     x, w, dy = case_data(cid)
     y, dx, dw = case_refs(cid)

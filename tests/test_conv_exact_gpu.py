@@ -8,6 +8,10 @@ partial sums must equal the integer sums (``==`` in float64), and the poison ban
 output must be untouched. The geometries are non-square, ragged in M and N, and small; the
 premises of the exactness argument are proven per case on the CPU (tests/test_conv_refs_cpu.py).
 
+The consumer-side BatchNorm-backward fold (bn_fold, DGRAD_BNF, WGRAD_GRAM, fold_bgemm, the
+k-combine of the split-K reduce) is held against the UNFOLDED definition -- dY = k1*dz + k2*y + k3
+formed in float64, then the plain conv backward -- so the algebra and the kernels are held together.
+
 Each test loops the compiled tiles its geometry is dispatched (``conv_refs.accepts``) and collects
 mismatches in a ``bad`` list; a launch the predicate accepts and the library rejects (-1 / -5) is
 a mismatch, any other launch error ends the test at once."""
@@ -265,7 +269,7 @@ def test_dgrad_exact(cid, dt):
 
 
 # ------------------------------------------------------------------ weight gradient
-def _wgrad_direct(K, dyd, xd, g, grad, ws, tile, k_chunk):
+def _wgrad_direct(K, dyd, xd, g, grad, ws, tile, k_chunk, pro=None, combine=None):
     """The launch of conv_wgrad at an explicit split depth (conv_wgrad caps splits at K / 256)."""
     import ctypes as C
     Nb = dyd.shape[0]
@@ -276,10 +280,12 @@ def _wgrad_direct(K, dyd, xd, g, grad, ws, tile, k_chunk):
     d = g.desc(Nb)
     st = K.stream(dyd.device)
     kbm, kbn = K._ktile(tile[0], tile[1], K._kdt(dyd))
+    sc, sh = pro or (None, None)
+    ck, cB, cs = combine or (None, None, None)
     K.check(K.ext.lib().pda_conv_wgrad(C.byref(d), K.ptr(dyd), K.ptr(xd), K.ptr(slab), splits, k_chunk,
-                                       None, None, K._kdt(dyd), kbm, kbn, st), "conv_wgrad")
+                                       K.ptr(sc), K.ptr(sh), K._kdt(dyd), kbm, kbn, st), "conv_wgrad")
     K.check(K.ext.lib().pda_wgrad_reduce(K.ptr(slab), K.ptr(grad), splits, M, N, int(math.log2(g.Cin)),
-                                         g.Cin, N, 1.0, 0, None, None, None, st), "wgrad_reduce")
+                                         g.Cin, N, 1.0, 0, K.ptr(ck), K.ptr(cB), K.ptr(cs), st), "wgrad_reduce")
 
 
 def _wgrad_case(K, cid, dtype, tiles, bna_tiles, bad, depths=(1, 64, 4096)):
@@ -412,6 +418,249 @@ def test_wgrad_stem_tap_exact(cid, dt):
     assert not bad, bad
 
 
+# ------------------------------------------------------------------ the consumer-side BatchNorm-backward fold
+def _fold_case(cid, dt):
+    """(case, dtype, operands, wf, b): the operands of a fold case with bn_fold's outputs from the
+    CPU model, so that a failure of a consumer names that kernel alone."""
+    dtype = R.DTYPES16[dt]
+    o = R.fold_operands(cid)
+    wf, b = R.bn_fold_ref(o["w"], o["k1"], o["k2"], o["k3"], dtype)
+    return R.FOLD_CASES[cid], dtype, o, wf, b
+
+
+def _kvec(o):
+    return _in(torch.cat([o["k1"], o["k2"], o["k3"]]), torch.float32)
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("cid", sorted(R.FOLD_CASES))
+def test_bn_fold_exact(cid, dt):
+    """bn_fold_kernel: both row blocks of Wf = [k1 o W ; W^T diag(k2) W] bit-equal, b = W^T k3 equal
+    as f32, G symmetric, guard bands around both outputs."""
+    K = _k()
+    c, dtype, o, wf, b = _fold_case(cid, dt)
+    out, wchk = _out((c.Cout + c.Cin, c.Cin), dtype)
+    bias, bchk = _out((c.Cin,), torch.float32)
+    K.bn_fold(_in(o["w"], dtype), _kvec(o), out, bias)
+    bad = []
+    _cmp(bad, "k1 o W", out[:c.Cout], R.round_to(wf[:c.Cout], dtype))
+    _cmp(bad, "G", out[c.Cout:], R.round_to(wf[c.Cout:], dtype))
+    _cmp(bad, "b", bias, b.to(torch.float32))
+    G = out[c.Cout:].cpu()
+    if not torch.equal(G, G.t()):
+        bad.append(("G", "not symmetric"))
+    _guards(bad, "bn_fold", wchk, bchk)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("cid", sorted(R.FOLD_CASES))
+def test_dgrad_bnf_exact(cid, dt):
+    """conv_dgrad_bnf on every compiled tile, with the Gram operand as it is and through the
+    prologue: plain dX bit-equal to the UNFOLDED float64 reference rounded once (the pixels no tap
+    lands on exactly +0, without the bias), and the fused BatchNorm-backward epilogue, modes 0-3
+    with and without g2: dz and the partial sums over the slabs. Wf and b come from the CPU model;
+    one extra launch takes them from the device's own bn_fold."""
+    K = _k()
+    c, dtype, o, wf, b = _fold_case(cid, dt)
+    g = _geom(K, c)
+    dzd, wfd, bd, xad = _in(o["dz"], dtype), _in(wf, dtype), _in(b, torch.float32), _in(o["xa"], dtype)
+    pro_d = (_f32(o["sc"]), _f32(o["sh"]))
+    od = {k: (_in(v, dtype) if v.dim() == 4 else _f32(v)) for k, v in R.epi_operands(cid).items()}
+    off = torch.ones(c.Nb, c.H, c.W, dtype=torch.bool)
+    off[:, ::c.stride, ::c.stride] = False          # the pixels of the parity classes without a tap
+    bad = []
+    for pro in (False, True):
+        V = R.dgrad_bnf_variants(cid, dtype, pro)
+        kw = dict(xa_pro=pro_d) if pro else {}
+        ref = R.round_to(V["plain"]["dx"], dtype)
+        maskd = _in(V[(3, False)]["mask"], torch.uint8)
+        for t in R.BNF_TILES:
+            assert R.accepts_bnf(t, c), (t, cid)
+            tag = (t, f"pro{int(pro)}", "plain")
+            dx, chk = _out(ref.shape, dtype)
+            if not _run(bad, tag, lambda: K.conv_dgrad_bnf(dzd, wfd, g, dx, xad, bd, tile=t, **kw)):
+                continue
+            _cmp(bad, tag, dx, ref)
+            if dx.view(torch.int16).cpu()[off].any().item():
+                bad.append((tag, "a pixel without a tap is not +0"))
+            _guards(bad, tag, chk)
+            G = K.dgrad_slabs(g, c.Nb, tile=t, dtype=dtype)
+            for key, v in V.items():
+                if key == "plain":
+                    continue
+                mode, wg = key
+                nq = 3 if mode == 2 else 2
+                part, pchk = _out((G * nq * c.Cin,), torch.float32)
+                dz2, zchk = _out(ref.shape, dtype)
+                y2 = od["y2"] if mode in (1, 2) else None
+                epi = K.ext.BnEpi(mode, nq, K.ptr(od["y"]), K.ptr(od["sc"]), K.ptr(od["sh"]), K.ptr(y2),
+                                  K.ptr(od["sc2"] if mode == 2 else None), K.ptr(od["sh2"] if mode == 2 else None),
+                                  K.ptr(od["g2"] if wg else None), K.ptr(part), K.ptr(maskd if mode == 3 else None))
+                tag = (t, f"pro{int(pro)}", f"epi{mode}" + ("+g2" if wg else ""))
+                if not _run(bad, tag, lambda: K.conv_dgrad_bnf(dzd, wfd, g, dz2, xad, bd, epi=epi, tile=t, **kw)):
+                    continue
+                _cmp(bad, tag, dz2, R.round_to(v["dz"], dtype))
+                tot = part.view(G, nq, c.Cin).double().sum(0).cpu()
+                if not torch.equal(tot, v["tot"]):
+                    bad.append((tag, "partial sums", (tot - v["tot"]).abs().max().item()))
+                _guards(bad, tag, zchk, pchk)
+    # the device's own bn_fold chained through, on the tile the wrapper picks
+    wf2, _ = _out((c.Cout + c.Cin, c.Cin), dtype)
+    b2, _ = _out((c.Cin,), torch.float32)
+    K.bn_fold(_in(o["w"], dtype), _kvec(o), wf2, b2)
+    dx, chk = _out(ref.shape, dtype)
+    K.conv_dgrad_bnf(dzd, wf2, g, dx, xad, b2, xa_pro=pro_d)
+    _cmp(bad, "bn_fold chained", dx, ref)
+    _guards(bad, "bn_fold chained", chk)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("cid", R.GRAM_CASES)
+def test_wgrad_gram_exact(cid, dt):
+    """pda_conv_wgrad_gram on every compiled tile at split depths from k_chunk = 64 to one split,
+    the slab of exactly splits * C * (C + 1) floats behind bands, reduced as the wrapper does: the
+    Gram rows and the column-sum row equal the integer reference, the Gram exactly symmetric; then
+    the conv_wgrad_gram wrapper once."""
+    import ctypes as C
+    K = _k()
+    c, dtype, o, _, _ = _fold_case(cid, dt)
+    Cc, P = c.Cin, c.M
+    yd, scd, shd = _in(o["xa"], dtype), _f32(o["sc"]), _f32(o["sh"])
+    gram, s = R.gram_ref(o["xa"], o["sc"], o["sh"], dtype)
+    ref = torch.cat([gram, s[None]]).to(torch.float32)
+    d = K.ConvGeom(c.Nb, c.H, c.W, Cc, Cc, 1, 1, 1, 0).desc(c.Nb)
+    L, st = K.ext.lib(), K.stream(torch.device(DEV))
+    bad = []
+
+    def sym(tag, ge):
+        gg = ge[:Cc].cpu()
+        if not torch.equal(gg, gg.t()):
+            bad.append((tag, "Gram not symmetric"))
+
+    for t in R.GRAM_TILES:
+        assert R.accepts_gram(t, c), (t, cid)
+        for k_chunk in sorted({64, 128, math.ceil(P / 64) * 64}):
+            splits = math.ceil(P / k_chunk)
+            tag = (t, k_chunk, splits)
+            slab, schk = _out((splits * Cc * (Cc + 1),), torch.float32)
+            ge, gchk = _out((Cc + 1, Cc), torch.float32)
+            if not _run(bad, tag, lambda: K.check(L.pda_conv_wgrad_gram(
+                    C.byref(d), K.ptr(yd), K.ptr(scd), K.ptr(shd), K.ptr(slab), splits, k_chunk,
+                    K.dt_of(dtype), t[0], t[1], st), "conv_wgrad_gram")):
+                continue
+            K.check(L.pda_wgrad_reduce(K.ptr(slab), K.ptr(ge), splits, Cc + 1, Cc, int(math.log2(Cc)), Cc, Cc,
+                                       1.0, 0, None, None, None, st), "gram_reduce")
+            _cmp(bad, tag, ge, ref)
+            sym(tag, ge)
+            _guards(bad, tag, schk, gchk)
+    ws = _GuardedWorkspace(K)
+    ge, gchk = _out((Cc + 1, Cc), torch.float32)
+    K.conv_wgrad_gram(yd, scd, shd, ge, ws)
+    _cmp(bad, "wrapper", ge, ref)
+    sym("wrapper", ge)
+    _guards(bad, "wrapper", gchk, *ws.checks)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("cid", R.GRAM_CASES)
+def test_fold_bgemm_exact(cid, dt):
+    """fold_bgemm: B = W Gram bit-equal as f32 (Cout above, equal to and below C)."""
+    K = _k()
+    c, dtype, o, _, _ = _fold_case(cid, dt)
+    gram, _ = R.gram_ref(o["xa"], o["sc"], o["sh"], dtype)
+    B, chk = _out((c.Cout, c.Cin), torch.float32)
+    K.fold_bgemm(_in(o["w"], dtype), _in(gram, torch.float32), B)
+    bad = []
+    _cmp(bad, "B", B, (o["w"] @ gram).to(torch.float32))
+    _guards(bad, "B", chk)
+    assert not bad, bad
+
+
+# (M, N, splits) of the direct reduce runs: M * N selects wgrad_reduce4_kernel<16, 32, 64, 128, 256>
+# (pda_wgrad_reduce halves the width while M * N / width < 256), N = 6 the scalar wgrad_reduce_kernel
+_REDUCE_SHAPES = [(64, 64, 67), (64, 128, 67), (128, 128, 67), (128, 256, 5), (256, 256, 5), (8, 6, 5)]
+
+
+def _reduce_combine_direct(K, bad):
+    """pda_wgrad_reduce with a combine on small synthetic integer slabs, one shape per kernel."""
+    L, st = K.ext.lib(), K.stream(torch.device(DEV))
+    for i, (M, N, splits) in enumerate(_REDUCE_SHAPES):
+        slab, B, s = R.ints((splits, M, N), 3, 300 + i), R.ints((M, N), 50, 310 + i), R.ints((N,), 20, 320 + i)
+        k = R.ints((3, M), 2, 330 + i)
+        ref = R.fold_combine_ref(slab.sum(0), k[0], k[1], k[2], B, s)
+        lg = int(math.log2(N)) if N % 4 == 0 else 3      # N = 6: one tap of 8 padded channels, 6 real
+        sd, kd, Bd, cd = (_in(v, torch.float32) for v in (slab, k, B, s))
+        for acc in (False, True):
+            pre = R.ints((M, N), 9, 340 + i)
+            grad, chk = _out((M, N), torch.float32, fill=pre if acc else None)
+            K.check(L.pda_wgrad_reduce(K.ptr(sd), K.ptr(grad), splits, M, N, lg, N, N, 0.25 if acc else 1.0,
+                                       int(acc), K.ptr(kd), K.ptr(Bd), K.ptr(cd), st), "wgrad_reduce")
+            _cmp(bad, ("reduce", M, N, acc), grad, ((pre + 0.25 * ref) if acc else ref).to(torch.float32))
+            _guards(bad, ("reduce", M, N, acc), chk)
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("cid", R.GRAM_CASES)
+def test_wgrad_combine_exact(cid, dt):
+    """The decomposed tail-fold weight gradient: conv_wgrad with the prologue and the k-combine in
+    the split-K reduce against dY^T a2 of the UNFOLDED definition, bit-equal as f32, on every
+    accepted tile at 1 and 4096 target blocks and at one split per 64 rows; scaled accumulation;
+    a ReduceBatch holding one combine and one plain reduction; pda_wgrad_reduce with a combine on
+    each of its kernels; and WGRAD_BNA with the forward prologue on X held to the same dW."""
+    K = _k()
+    c, dtype, o, _, _ = _fold_case(cid, dt)
+    g = _geom(K, c)
+    r = R.fold_refs(cid, dtype, True)
+    gram, s = R.gram_ref(o["xa"], o["sc"], o["sh"], dtype)
+    ref = r["dw"].to(torch.float32)
+    dzd, xad, yd = _in(o["dz"], dtype), _in(o["xa"], dtype), _in(r["y"], dtype)
+    pro = (_f32(o["sc"]), _f32(o["sh"]))
+    kk = _kvec(o)
+    comb = (kk, _in(o["w"] @ gram, torch.float32), _in(s, torch.float32))
+    ws = _GuardedWorkspace(K)
+    bad = []
+
+    def one(tag, fn, want=ref, fill=None):
+        dw, chk = _out(want.shape, torch.float32, fill=fill)
+        if _run(bad, tag, lambda: fn(dw.view(-1))):
+            _cmp(bad, tag, dw, want)
+            _guards(bad, tag, chk)
+
+    tiles = [t for t in R.PASS_TILES["wgrad"] if R.accepts("wgrad", t, c) and t[0] < 1000]
+    assert tiles
+    for t in tiles:
+        for tb in (1, 4096):
+            one((t, f"tb{tb}"), lambda gr: K.conv_wgrad(dzd, xad, g, gr, ws, tile=t, target_blocks=tb,
+                                                        pro=pro, combine=comb))
+        one((t, "k64"), lambda gr: _wgrad_direct(K, dzd, xad, g, gr, ws, t, 64, pro, comb))
+    for t in R.BNA_TILES:
+        if R.accepts_bna(t, c):
+            for tb in (1, 4096):
+                one((t, f"bna+pro/tb{tb}"), lambda gr: K.conv_wgrad(dzd, xad, g, gr, ws, tile=t, target_blocks=tb,
+                                                                   bna=(yd, kk), pro=pro))
+    pre = R.ints(ref.shape, 9, 61)
+    one("accumulate", lambda gr: K.conv_wgrad(dzd, xad, g, gr, ws, tile=tiles[0], scale=0.25, accumulate=True,
+                                              pro=pro, combine=comb),
+        want=(pre + 0.25 * r["dw"]).to(torch.float32), fill=pre)
+    # one combine and one plain reduction queued, one launch
+    ws.reduce_batch = K.ReduceBatch(ws)
+    plain = (o["dz"].reshape(-1, c.Cout).t() @ r["a2"].reshape(-1, c.Cin)).to(torch.float32)
+    (dw1, chk1), (dw2, chk2) = _out(ref.shape, torch.float32), _out(ref.shape, torch.float32)
+    K.conv_wgrad(dzd, xad, g, dw1.view(-1), ws, tile=tiles[0], target_blocks=64, pro=pro, combine=comb)
+    K.conv_wgrad(dzd, xad, g, dw2.view(-1), ws, tile=tiles[-1], target_blocks=64, pro=pro)
+    ws.reduce_batch.flush()
+    ws.reduce_batch = None
+    _cmp(bad, "batch/combine", dw1, ref)
+    _cmp(bad, "batch/plain", dw2, plain)
+    _guards(bad, "batch", chk1, chk2)
+    _reduce_combine_direct(K, bad)
+    _guards(bad, "workspace", *ws.checks)
+    assert not bad, bad
+
+
 # ------------------------------------------------------------------ the f32 kernels
 @pytest.mark.parametrize("mode", ["exact", "split"])
 @pytest.mark.parametrize("cid", [i for i in sorted(R.CASES) if R.CASES[i].f32])
@@ -475,3 +724,11 @@ def test_every_compiled_tile_ran_somewhere():
         for pas in c.passes:
             assert any(R.accepts(pas, t, c) for t in R.PASS_TILES[pas]), (c.id, pas)
     assert {R.CASES[i].Cout for i in R.CASES if R.tail_ok(R.CASES[i])} >= {64, 128}   # both FWD_TAIL tiles
+    # the fold: the lists are the compiled BNF_CASE / GRAM_CASE tables of both dtypes, and every tile
+    # is accepted by a fold case (test_dgrad_bnf_exact / test_wgrad_gram_exact run every tile on every case)
+    assert R.compiled_tiles("BNF_CASE") == {"DT_BF16": R.BNF_TILES, "DT_F16": R.BNF_TILES}
+    assert R.compiled_tiles("GRAM_CASE") == {"DT_BF16": R.GRAM_TILES, "DT_F16": R.GRAM_TILES}
+    for t in R.BNF_TILES:
+        assert any(R.accepts_bnf(t, c) for c in R.FOLD_CASES.values()), t
+    for t in R.GRAM_TILES:
+        assert any(R.accepts_gram(t, R.FOLD_CASES[i]) for i in R.GRAM_CASES), t

@@ -123,6 +123,13 @@ def test_exact_conditions_fail_loudly():
         R.assert_exact_conditions("acc", acc_abs=(torch.tensor([2.0 ** 24], dtype=F64),))
     with pytest.raises(AssertionError):   # 256 rows of (256 + 256)^2 = 2^26
         R.assert_exact_conditions("stats", stats_of=(torch.full((256, 1), 256.0, dtype=F64),))
+    # a fold whose G = W^T diag(k2) W = 257 no 16-bit format of 8 significant bits holds (the model
+    # would round it to 256 and the test would then hold the kernel to a rounding, not to the algebra)
+    w, one = torch.ones(257, 1, dtype=F64), torch.ones(257, dtype=F64)
+    R.assert_fold_operands_exact("ok", w[:256], one[:256], one[:256], one[:256])
+    assert R.bn_fold_ref(w, one, one, one, torch.bfloat16)[0][257].item() == 256.0
+    with pytest.raises(AssertionError):
+        R.assert_fold_operands_exact("G", w, one, one, one)
 
 
 def test_guarded_buffer_bands():
@@ -142,7 +149,7 @@ def test_guarded_buffer_bands():
 
 
 @pytest.mark.parametrize("dt", sorted(R.DTYPES16))
-@pytest.mark.parametrize("cid", sorted(R.CASES))
+@pytest.mark.parametrize("cid", sorted(set(R.CASES) | set(R.FOLD_CASES)))
 def test_gpu_cases_stay_within_exact_conditions(cid, dt):
     R.check_case_conditions(cid, R.DTYPES16[dt])
 
@@ -171,3 +178,119 @@ def test_every_compiled_tile_and_geometry_is_covered():
         for pas in c.passes:
             assert any(R.accepts(pas, t, c) for t in R.PASS_TILES[pas]), (c.id, pas)
     assert {c.id for c in R.CASES.values() if c.f32} == {"A", "C", "D", "F"}
+    # the fold: the lists are the compiled tables, for both dtypes, and every tile runs somewhere
+    assert R.compiled_tiles("BNF_CASE") == {"DT_BF16": R.BNF_TILES, "DT_F16": R.BNF_TILES}
+    assert R.compiled_tiles("GRAM_CASE") == {"DT_BF16": R.GRAM_TILES, "DT_F16": R.GRAM_TILES}
+    assert R.compiled_tiles("BNA_CASE") == {"DT_BF16": R.BNA_TILES, "DT_F16": R.BNA_TILES}
+    for t in R.BNF_TILES:
+        assert any(R.accepts_bnf(t, c) for c in R.FOLD_CASES.values()), t
+    for t in R.GRAM_TILES:
+        assert any(R.accepts_gram(t, R.FOLD_CASES[i]) for i in R.GRAM_CASES), t
+    fc = R.FOLD_CASES.values()
+    assert all(R.accepts_bnf(t, c) for c in fc for t in R.BNF_TILES)      # every case runs every tile
+    assert {c.M % 64 != 0 and c.M % 128 != 0 for c in fc} == {True}       # ragged against both heights
+    assert {c.Cin for c in fc} >= {64, 128, 256} and {c.stride for c in fc} == {1, 2}
+    assert any(c.Cout > c.Cin for c in fc) and any(c.Cout < c.Cin for c in fc)
+    gc = [R.FOLD_CASES[i] for i in R.GRAM_CASES]       # Gram: P below 64, and splits with a short last one
+    assert {c.Cin for c in gc} >= {64, 128, 256} and min(c.M for c in gc) < 64
+    assert any(c.M > 128 and c.M % 64 for c in gc)
+
+
+# ------------------------------------------------------------------ the consumer-side fold
+def _fold_tiny(stride, dtype):
+    """A tiny fold problem (Cout 6, Cin 4) with the prologue: operands and the autograd result of
+    the UNFOLDED definition -- BN-backward apply dY = k1*dz + k2*y + k3, then conv2d's backward."""
+    c = R.Case("t", 2, 4, 6, 4, 6, 1, 1, stride, 0)
+    w, dz = R.ints((c.Cout, c.Cin), 1, 11), R.ints((c.Nb, c.Ho, c.Wo, c.Cout), 2, 12)
+    xa = R.ints((c.Nb, c.H, c.W, c.Cin), 2, 13)
+    k1, k2 = R.coeffs(c.Cout, 14)
+    k3 = R.ints((c.Cout,), 1, 15)
+    sc, sh = R.coeffs(c.Cin, 16)
+    a2 = torch.relu(xa * sc + sh)
+    xr = a2.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    wr = w.reshape(c.Cout, c.Cin, 1, 1).clone().requires_grad_(True)
+    y = torch.nn.functional.conv2d(xr, wr, stride=stride)
+    dY = k1.view(1, -1, 1, 1) * dz.permute(0, 3, 1, 2) + k2.view(1, -1, 1, 1) * y.detach() + k3.view(1, -1, 1, 1)
+    y.backward(dY)
+    return c, dict(w=w, dz=dz, xa=xa, k1=k1, k2=k2, k3=k3, sc=sc, sh=sh, a2=a2,
+                   dx=xr.grad.permute(0, 2, 3, 1), dw=wr.grad.reshape(c.Cout, c.Cin))
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("stride", [1, 2])
+def test_fold_models_against_loops_and_autograd(stride, dtype):
+    c, o = _fold_tiny(stride, dtype)
+    w, k1, k2, k3 = o["w"], o["k1"], o["k2"], o["k3"]
+    wf, b = R.bn_fold_ref(w, k1, k2, k3, dtype)
+    wn, G, bn = w.numpy(), np.zeros((c.Cin, c.Cin)), np.zeros(c.Cin)
+    for i in range(c.Cin):
+        for k in range(c.Cout):
+            bn[i] += wn[k, i] * k3[k].item()
+            for j in range(c.Cin):
+                G[i, j] += wn[k, i] * (k2[k].item() * wn[k, j])
+    assert torch.equal(wf[:c.Cout], k1[:, None] * w) and torch.equal(wf[c.Cout:], torch.from_numpy(G))
+    assert torch.equal(b, torch.from_numpy(bn)) and torch.equal(wf[c.Cout:], wf[c.Cout:].t())
+    # dX: the folded sum on the landing pixels, exact zeros elsewhere (no bias there)
+    a2s = o["a2"][:, ::stride, ::stride]
+    fold = o["dz"] @ wf[:c.Cout] + a2s @ wf[c.Cout:] + b
+    want = torch.zeros_like(o["dx"])
+    want[:, ::stride, ::stride] = fold
+    assert torch.equal(o["dx"], want) and o["dx"].abs().max() > 0
+    # Gram, column sums and the combine against loops; dW against autograd
+    gram, s = R.gram_ref(o["xa"], o["sc"], o["sh"], dtype)
+    a = o["a2"].reshape(-1, c.Cin).numpy()
+    gn = np.zeros((c.Cin, c.Cin))
+    for p in range(a.shape[0]):
+        gn += np.outer(a[p], a[p])
+    assert torch.equal(gram, torch.from_numpy(gn)) and torch.equal(s, torch.from_numpy(a.sum(0)))
+    if stride == 1:
+        S, B = o["dz"].reshape(-1, c.Cout).t() @ o["a2"].reshape(-1, c.Cin), w @ gram
+        comb = R.fold_combine_ref(S, k1, k2, k3, B, s)
+        for n1 in range(c.Cout):
+            for n2 in range(c.Cin):
+                assert comb[n1, n2] == k1[n1] * S[n1, n2] + k2[n1] * B[n1, n2] + k3[n1] * s[n2]
+        assert torch.equal(comb, o["dw"]) and o["dw"].abs().max() > 0
+
+
+@pytest.mark.parametrize("dt", sorted(R.DTYPES16))
+@pytest.mark.parametrize("cid", sorted(R.FOLD_CASES))
+def test_fold_identities_hold_exactly(cid, dt):
+    """On every fold case of the GPU file: the folded sums the kernels compute, built from the
+    models, equal the unfolded float64 references (``fold_refs``) element for element."""
+    c, dtype = R.FOLD_CASES[cid], R.DTYPES16[dt]
+    o = R.fold_operands(cid)
+    wf, b = R.bn_fold_ref(o["w"], o["k1"], o["k2"], o["k3"], dtype)
+    for pro in (False, True):
+        r = R.fold_refs(cid, dtype, pro)
+        want = torch.zeros_like(r["dx"])
+        want[:, ::c.stride, ::c.stride] = o["dz"] @ wf[:c.Cout] + r["a2"][:, ::c.stride, ::c.stride] @ wf[c.Cout:] + b
+        assert torch.equal(r["dx"], want)
+        if c.stride == 2:
+            assert r["dx"][:, 1::2].abs().max() == 0 and r["dx"][:, :, 1::2].abs().max() == 0
+        V = R.dgrad_bnf_variants(cid, dtype, pro)
+        assert torch.equal(V["plain"]["dx"], R.r64(want, dtype)) and len(V) == 1 + len(R.EPI_VARIANTS)
+    if cid in R.GRAM_CASES:
+        r = R.fold_refs(cid, dtype, True)
+        gram, s = R.gram_ref(o["xa"], o["sc"], o["sh"], dtype)
+        a2 = r["a2"].reshape(-1, c.Cin)
+        assert torch.equal(gram, a2.t() @ a2) and torch.equal(gram, gram.t())
+        S = o["dz"].reshape(-1, c.Cout).t() @ a2
+        assert torch.equal(R.fold_combine_ref(S, o["k1"], o["k2"], o["k3"], o["w"] @ gram, s), r["dw"])
+        # the WGRAD_BNA form of the same gradient: dY is representable, so its rounding is the identity
+        assert torch.equal(R.bna_ref(o["dz"], r["y"], o["k1"], o["k2"], o["k3"], dtype), r["dY"])
+
+
+def test_fold_wrappers_refuse_a_channel_count_that_is_no_power_of_two():
+    """The split-K reduce decodes a slab column by a shift: a truncated log2 would scatter the
+    columns without an error. No launch."""
+    from pytorch_distributed_amd.ops import native_ops as K
+    C = 192
+    y = torch.zeros(1, 2, 2, C, dtype=torch.bfloat16)
+    v = torch.zeros(C)
+    with pytest.raises(ValueError, match="power of two"):
+        K.conv_wgrad_gram(y, v, v, torch.zeros(C + 1, C), K.Workspace("cpu"))
+    g = K.ConvGeom(1, 2, 2, C, 64, 1, 1, 1, 0)
+    dz = torch.zeros(1, 2, 2, 64, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="power-of-two"):
+        K.conv_wgrad(dz, y, g, torch.zeros(64 * C), K.Workspace("cpu"),
+                     combine=(torch.zeros(192), torch.zeros(64, C), v))
