@@ -61,6 +61,9 @@ class RunConfig:
     ema_warmup: bool = True          # EMA decay min(decay, (1 + t) / (10 + t)) over its updates t
     clip_grad_norm: float = 0.0      # maximum global L2 norm of the gradient (0 = off)
     random_erase: float = 0.0        # random-erasing probability p in [0, 1] (0 = off)
+    opt: str = "sgd"                 # sgd | adamw | lamb
+    betas: tuple = (0.9, 0.999)      # AdamW / LAMB moment decays b1, b2 in [0, 1)
+    opt_eps: float = 1e-8            # AdamW / LAMB eps
 
     @property
     def soft_targets(self) -> bool:
@@ -81,6 +84,13 @@ SCRIPT_DEFAULTS = {
 
 def _bool(s: str) -> bool:
     return s not in ("", "0", "false", "False")
+
+
+def _betas(s: str) -> tuple:
+    b = tuple(float(x) for x in s.split(","))
+    if len(b) != 2:
+        raise ValueError(f"MX_BETAS is 'b1,b2', got {s!r}")
+    return b
 
 
 _ENV = {
@@ -120,6 +130,10 @@ _ENV = {
     "MX_EMA_WARMUP": ("ema_warmup", _bool),
     "MX_CLIP_GRAD_NORM": ("clip_grad_norm", float),
     "MX_RANDOM_ERASE": ("random_erase", float),
+    "MX_OPT": ("opt", str),
+    "MX_BETAS": ("betas", _betas),
+    "MX_OPT_EPS": ("opt_eps", float),
+    "MX_WEIGHT_DECAY": ("weight_decay", float),
 }
 
 
@@ -180,6 +194,15 @@ def config_for(script: str, env: Optional[dict] = None,
     if not 0 <= cfg.random_erase <= 1:
         raise ValueError(f"MX_RANDOM_ERASE is a probability in [0, 1] (0 = off), got "
                          f"{cfg.random_erase!r}")
+    if cfg.opt not in ("sgd", "adamw", "lamb"):
+        raise ValueError(f"MX_OPT must be sgd|adamw|lamb, got {cfg.opt!r}")
+    if not all(0 <= b < 1 for b in cfg.betas):
+        raise ValueError(f"MX_BETAS are two moment decays in [0, 1), got {cfg.betas!r}")
+    for var, v in (("MX_OPT_EPS", cfg.opt_eps), ("MX_WEIGHT_DECAY", cfg.weight_decay)):
+        if not v >= 0 or v == float("inf"):
+            raise ValueError(f"{var} is a finite number >= 0, got {v!r}")
+    if cfg.opt != "sgd" and (cfg.nesterov or cfg.lars > 0):
+        raise ValueError(f"MX_NESTEROV / MX_LARS belong to SGD: drop them or MX_OPT={cfg.opt}")
     if cfg.nesterov and not cfg.momentum > 0:
         raise ValueError("MX_NESTEROV needs momentum > 0")
     if cfg.data.startswith("packed:") and not cfg.data.split(":", 1)[1]:

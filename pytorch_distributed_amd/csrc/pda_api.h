@@ -308,6 +308,42 @@ int pda_sgd_seg(float* p, const float* g, float* buf, void* shadow, long long n,
                 const double* slab, const float* scale, const float* found_inf, int flags, int dt,
                 hipStream_t st);
 
+// ------------------------------------------------------------------ adam.hip
+// AdamW / LAMB over the segment and block tables of optim.hip (SegRow / BlkRow give the geometry;
+// their hyper-parameter fields are not read). hyper: pda_adam_floats() floats per segment --
+//   [0] lr  [1] b1  [2] b2  [3] eps  [4] wd  [5] lamb (0 / 1)  [6] (float)(1 - b1)  [7] (float)(1 - b2)
+//   [8] (float)(b1 - [1])  [9] (float)(b2 - [2])   (the rest unused)
+// with 1 - b and b - (float)b evaluated in double by whoever fills the table. bias: 2 floats per
+// segment (c1, c2), written by pda_adam_tick; step: one int32, the number of applied steps.
+// *_host tables are validated, *_dev tables (the same bytes) are read by the kernels. Beside
+// pda_seg_check's codes: -7 lr negative or not finite, -8 a beta outside [0, 1), -9 eps negative or
+// not finite, -10 weight decay negative or not finite, -11 a segment has LAMB on (pda_adamw_seg
+// does not take one), -12 a segment has LAMB on and there is no slab.
+int pda_adam_floats();
+int pda_adam_check(const float* hyper, int nseg);
+// One block: step[0] += 1 and the bias corrections of every segment for the new count; nothing at
+// all when found_inf (nullable) is set.
+int pda_adam_tick(const float* hyper_dev, const float* hyper_host, int nseg, int* step, float* bias,
+                  const float* found_inf, hipStream_t st);
+// flags bit1: write the 16-bit shadow (dt). scale / found_inf as pda_sgd_seg.
+int pda_adamw_seg(float* p, const float* g, float* m, float* v, void* shadow, long long n,
+                  const void* seg_dev, const void* blk_dev, const void* seg_host, const void* blk_host,
+                  int nseg, int nblk, const float* hyper_dev, const float* hyper_host,
+                  const float* bias, const float* scale, const float* found_inf, int flags, int dt,
+                  hipStream_t st);
+// LAMB, phase A: m, v updated; per block sum p^2 and sum u^2 into slab (2 * nblk doubles).
+int pda_lamb_moments(const float* p, const float* g, float* m, float* v, long long n,
+                     const void* seg_dev, const void* blk_dev, const void* seg_host,
+                     const void* blk_host, int nseg, int nblk, const float* hyper_dev,
+                     const float* hyper_host, const float* bias, double* slab, const float* scale,
+                     const float* found_inf, hipStream_t st);
+// LAMB, phase B: the trust ratio from the slab, p and the shadow written (g is not read).
+int pda_lamb_apply(float* p, const float* m, const float* v, void* shadow, long long n,
+                   const void* seg_dev, const void* blk_dev, const void* seg_host,
+                   const void* blk_host, int nseg, int nblk, const float* hyper_dev,
+                   const float* hyper_host, const float* bias, const double* slab,
+                   const float* found_inf, int flags, int dt, hipStream_t st);
+
 // ------------------------------------------------------------------ clip.hip
 // Host-side validation of a clip launch: blks (nblk BlkRow rows, `seg` unused) against a flat
 // gradient of n elements. 0 = good; otherwise the negative code that ops/native_ops.py turns into a

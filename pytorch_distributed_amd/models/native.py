@@ -40,11 +40,11 @@ from torch import nn
 from ..ops import ext
 from ..ops import native_ops as K
 from ..ops.native_ops import ConvGeom, Workspace
-from .native_train import (NativeCrossEntropy, NativeSGD, NativeTrainer,  # noqa: F401 (re-exported)
+from .native_train import (NativeAdamW, NativeCrossEntropy, NativeSGD, NativeTrainer,  # noqa: F401 (re-exported)
                            _XentFn, _XentSoftFn)
 from .resnet import Bottleneck, ResNet
 
-__all__ = ["NativeResNet", "NativeSGD", "NativeCrossEntropy", "NativeTrainer", "supports"]
+__all__ = ["NativeResNet", "NativeSGD", "NativeAdamW", "NativeCrossEntropy", "NativeTrainer", "supports"]
 
 ALIGN = 64  # elements; keeps every segment 16-B aligned in the 16-bit shadow
 # DDP bucket boundaries (block boundaries of the flat gradient) are padded to multiples of
@@ -1190,11 +1190,16 @@ class NativeResNet(nn.Module):
         with torch.no_grad():
             return self.native_forward(x, train=train, save=False)
 
-    def make_optimizer(self, lr=0.1, momentum=0.9, weight_decay=1e-4, nesterov=False, lars=0.0,
-                       lars_eps=1e-8, param_groups=None, clip_grad_norm=0.0) -> "NativeSGD":
-        return NativeSGD(self, lr=lr, momentum=momentum, weight_decay=weight_decay,
-                         nesterov=nesterov, lars=lars, lars_eps=lars_eps, param_groups=param_groups,
-                         clip_grad_norm=clip_grad_norm)
+    def make_optimizer(self, *args, opt: str = "sgd", **kw):
+        """``opt="sgd"`` (the default): :class:`NativeSGD` with its arguments (lr, momentum,
+        weight_decay, nesterov, lars, lars_eps, param_groups, clip_grad_norm). ``"adamw"`` /
+        ``"lamb"``: :class:`NativeAdamW` with its arguments (lr, betas, eps, weight_decay,
+        param_groups, clip_grad_norm), the groups' ``lamb`` default off / on."""
+        if opt == "sgd":
+            return NativeSGD(self, *args, **kw)
+        if opt not in ("adamw", "lamb"):
+            raise ValueError(f"make_optimizer: opt is sgd, adamw or lamb, got {opt!r}")
+        return NativeAdamW(self, *args, lamb=opt == "lamb", **kw)
 
     def make_criterion(self, label_smoothing: float = 0.0) -> "NativeCrossEntropy":
         return NativeCrossEntropy(self, label_smoothing)

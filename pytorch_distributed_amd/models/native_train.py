@@ -1,5 +1,5 @@
 """Loss, optimizer and bench trainer of the native engine (``models/native.py``): the fused
-cross-entropy nodes, the flat-buffer SGD and the trainer ``bench.py`` drives. None of them knows the
+cross-entropy nodes, the flat-buffer SGD, AdamW / LAMB and the trainer ``bench.py`` drives. None of them knows the
 forward / backward schedule; the loss hands its 16-bit d(loss)/d(logits) to the network through
 ``NativeResNet._pending_dlog16``."""
 from __future__ import annotations
@@ -14,7 +14,7 @@ from ..ops import native_ops as K
 if TYPE_CHECKING:
     from .native import NativeResNet
 
-__all__ = ["NativeSGD", "NativeCrossEntropy", "NativeTrainer"]
+__all__ = ["NativeSGD", "NativeAdamW", "NativeCrossEntropy", "NativeTrainer"]
 
 
 class _XentFn(torch.autograd.Function):
@@ -302,6 +302,179 @@ class NativeSGD(torch.optim.Optimizer):
                         st["momentum_buffer"] = self._views[p]
                         any_buf = True
             self._initialized = any_buf
+
+
+class NativeAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW semantics (amsgrad off) and, with ``lamb``, the LAMB layer-wise trust ratio
+    on top of the same moments, executed as segmented kernels over the flat buffers
+    (``csrc/adam.hip``; the update is spelled out in ``pytorch_distributed_amd/optim.py``). A step is
+    ``adam_tick`` (one block: the device step counter and every tensor's bias corrections) and then
+    either ``adamw_seg`` -- one launch that reads p, g, m, v and writes p, m, v and the 16-bit shadow
+    -- or, when some group has ``lamb`` on, ``lamb_moments`` + ``lamb_apply``. No host sync, no
+    allocation, no ATen launch.
+
+    ``param_groups`` are torch-style dicts: ``params`` plus any of ``lr``, ``betas``, ``eps``,
+    ``weight_decay``, ``lamb`` (the constructor arguments are the defaults). Parameters in no group
+    are frozen and never touched; the groups are fixed at construction; a scheduler may edit their
+    values between steps (the float table is uploaded again when it did). The state is two flat
+    buffers beside ``flat_params`` (``exp_avg``, ``exp_avg_sq``) and a step counter on the device,
+    which advances only on steps that were applied: an AMP step skipped for an overflow leaves it,
+    as ``GradScaler`` leaves ``torch.optim.AdamW``'s. ``state_dict()`` has ``torch.optim.AdamW``'s
+    format, so checkpoints interchange; it reads the counter to the host.
+
+    ``clip_grad_norm``, ``grad_norm``, ``step_amp``, ``zero_grad`` and the stale-gradient guard are
+    :class:`NativeSGD`'s. ``segmented`` is always True: the captured-step paths refuse this
+    optimizer as they refuse the segmented SGD."""
+
+    segmented = True
+
+    def __init__(self, model: NativeResNet, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 lamb=False, param_groups=None, clip_grad_norm=0.0) -> None:
+        from ..optim import (_ADAM_CARRIED, ADAM_GROUP_KEYS, check_adam_hyper,
+                             normalize_param_groups)
+        self._sealed = False
+        if (not isinstance(clip_grad_norm, (int, float)) or isinstance(clip_grad_norm, bool)
+                or not clip_grad_norm >= 0 or clip_grad_norm == float("inf")):
+            raise ValueError(f"NativeAdamW: clip_grad_norm is a finite maximum norm >= 0 (0 = off), "
+                             f"got {clip_grad_norm!r}")
+        self.clip_grad_norm = float(clip_grad_norm)
+        defaults = dict(lr=lr, betas=tuple(betas) if isinstance(betas, list) else betas, eps=eps,
+                        weight_decay=weight_decay, lamb=bool(lamb), amsgrad=False, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None)
+        groups = normalize_param_groups(list(model.parameters()), param_groups, defaults,
+                                        keys=ADAM_GROUP_KEYS, carried=_ADAM_CARRIED,
+                                        check=check_adam_hyper, who="NativeAdamW")
+        if not any(g["params"] for g in groups):
+            raise ValueError("NativeAdamW: the parameter groups hold no parameter")
+        super().__init__(groups, defaults)
+        self._sealed = True
+        self.model = model
+        fp = model.flat_params
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(fp), torch.zeros_like(fp)
+        self._amp_ws = None    # step_amp's scan counters and 1/scale, allocated on its device
+        self._amp_inv = None
+        # per-parameter views of both moments (torch format in state_dict; conv weights as OIHW)
+        self._views = {}
+        base = fp.data_ptr()
+        segments = []
+        for g in self.param_groups:
+            for p in g["params"]:
+                off = (p.data_ptr() - base) // 4
+                segments.append((off, p.numel()))
+                vs = []
+                for flat in (self.exp_avg, self.exp_avg_sq):
+                    v = flat[off:off + p.numel()]
+                    if p.dim() == 4:
+                        O, I, R, S_ = p.shape
+                        v = v.view(O, R, S_, I).permute(0, 3, 1, 2)
+                    else:
+                        v = v.view(p.shape)
+                    vs.append(v)
+                self._views[p] = tuple(vs)
+        self._uploaded = self._hyper_rows()
+        self._tables = K.adam_tables(segments, self._uploaded, fp.device)
+        self.grad_norm = None
+        if self.clip_grad_norm > 0:    # every buffer of the clip launch, once (as NativeSGD)
+            self._clip_slab = torch.zeros(self._tables.nblocks, dtype=torch.float64, device=fp.device)
+            self._clip_cnt = torch.zeros(1, dtype=torch.int32, device=fp.device)
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=fp.device)
+            self.grad_norm = self._clip_out[0:1]
+
+    def add_param_group(self, param_group) -> None:
+        if getattr(self, "_sealed", False):
+            raise ValueError("NativeAdamW: the groups are fixed at construction (the segment table "
+                             "is built once); pass param_groups to the constructor")
+        super().add_param_group(param_group)
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        self.model.zero_grad_flat()
+
+    def _hyper_rows(self) -> list:
+        """One hyper-parameter row per segment, from the groups as they are now."""
+        from ..optim import ADAM_GROUP_KEYS, check_adam_hyper
+        rows = []
+        for i, g in enumerate(self.param_groups):
+            check_adam_hyper(g, f"NativeAdamW: param_groups[{i}]: ")
+            h = {k: g[k] for k in ADAM_GROUP_KEYS}
+            h["betas"], h["lamb"] = tuple(h["betas"]), bool(h["lamb"])
+            rows += [h] * len(g["params"])
+        return rows
+
+    def _launch(self, inv_scale=None, found_inf=None) -> None:
+        m = self.model
+        if m._grads_zero:      # zero_grad() and no backward since: see NativeSGD._launch
+            return
+        t = self._tables
+        rows = self._hyper_rows()
+        if rows != self._uploaded:      # a scheduler (or the user) edited a group since the last step
+            t.set_hyper(rows)
+            self._uploaded = rows
+        if self.clip_grad_norm > 0:
+            K.grad_clip(m.flat_grad, t.seg, self.clip_grad_norm, self._clip_slab, self._clip_cnt,
+                        self._clip_out, inv_scale=inv_scale, found_inf=found_inf)
+            inv_scale = self._clip_out[1:2]
+        shadow = None if m.f32 else m.flat_shadow
+        K.adam_tick(t, found_inf)
+        if t.any_lamb:
+            K.lamb_moments(m.flat_params, m.flat_grad, self.exp_avg, self.exp_avg_sq, t,
+                           inv_scale=inv_scale, found_inf=found_inf)
+            K.lamb_apply(m.flat_params, self.exp_avg, self.exp_avg_sq, shadow, t, found_inf=found_inf)
+        else:
+            K.adamw_seg(m.flat_params, m.flat_grad, self.exp_avg, self.exp_avg_sq, shadow, t,
+                        inv_scale=inv_scale, found_inf=found_inf)
+        m._pack_stem()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        self._launch()
+        return loss
+
+    @torch.no_grad()
+    def step_amp(self, scale: torch.Tensor, found_inf: torch.Tensor, tracker=None,
+                 growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000) -> None:
+        """AMP step with no host sync: ``amp_scan`` (as :meth:`NativeSGD.step_amp`), then the
+        launches of :meth:`step`, every one of which returns at once when found_inf is set."""
+        if self._amp_ws is None or self._amp_ws.device != scale.device:
+            self._amp_ws = torch.zeros(2, dtype=torch.int32, device=scale.device)
+            self._amp_inv = torch.ones(1, dtype=torch.float32, device=scale.device)
+        K.amp_scan(self.model.flat_grad, found_inf, self._amp_inv, scale, tracker, self._amp_ws,
+                   growth_factor, backoff_factor, growth_interval)
+        self._launch(inv_scale=self._amp_inv, found_inf=found_inf)
+
+    def state_dict(self):
+        t = int(self._tables.step.item())
+        if t > 0:    # (torch.optim.AdamW has no state before its first step either)
+            for g in self.param_groups:
+                for p in g["params"]:
+                    m, v = self._views[p]
+                    self.state[p] = {"step": torch.tensor(float(t)), "exp_avg": m, "exp_avg_sq": v}
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        lamb = [g["lamb"] for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, on in zip(self.param_groups, lamb):
+            g.setdefault("lamb", on)     # a plain torch.optim.AdamW checkpoint: each group keeps its own
+            for k, v in self.defaults.items():
+                g.setdefault(k, v)
+        steps = set()
+        with torch.no_grad():
+            self.exp_avg.zero_(), self.exp_avg_sq.zero_()    # (a checkpoint from before the first step)
+            for g in self.param_groups:
+                for p in g["params"]:
+                    st = self.state.get(p, {})
+                    if "exp_avg" not in st:
+                        continue
+                    for view, key in zip(self._views[p], ("exp_avg", "exp_avg_sq")):
+                        view.copy_(st[key])
+                        st[key] = view
+                    steps.add(int(st["step"]))
+            if len(steps) > 1:
+                raise ValueError(f"NativeAdamW: one step count serves every parameter; the "
+                                 f"checkpoint holds {sorted(steps)}")
+            self._tables.step.fill_(steps.pop() if steps else 0)
 
 
 # ------------------------------------------------------------------ bench trainer

@@ -31,6 +31,7 @@ __all__ = [
     "pack_stem", "synth_batch", "Workspace", "aug_check", "aug_resize",
     "aug_draw", "aug_resize_dev", "aug_record_bytes", "batch_layout", "batch_shape",
     "FLAT_CHUNK", "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg", "grad_clip",
+    "ADAM_HYPER", "AdamTables", "adam_tables", "adam_tick", "adamw_seg", "lamb_moments", "lamb_apply",
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
     "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
 ]
@@ -1431,6 +1432,135 @@ def sgd_seg(p, g, buf, shadow, tables: SegTables, initialized: bool, inv_scale=N
                                ptr(tables.slab), ptr(inv_scale), ptr(found_inf), flags, dt,
                                stream(p.device))
     _seg_check(rc, "sgd_seg")
+
+
+# ------------------------------------------------------------------ AdamW / LAMB (csrc/adam.hip)
+ADAM_HYPER = 12       # floats per segment of the hyper-parameter table (pda_adam_floats)
+_ADAM_KEYS = ("lr", "betas", "eps", "weight_decay", "lamb")
+_ADAM_ERRORS = {**_SEG_ERRORS, -7: "lr must be finite and >= 0", -8: "the betas must lie in [0, 1)",
+                -9: "eps must be finite and >= 0", -10: "weight_decay must be finite and >= 0",
+                -11: "a segment has LAMB on: it needs lamb_moments + lamb_apply, not adamw_seg",
+                -12: "a segment has LAMB on and the tables have no slab"}
+
+
+def _f32(x: float) -> float:
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+class AdamTables:
+    """What the AdamW / LAMB launches share: the segment and block tables (``seg``, a
+    :class:`SegTables`: the geometry), the float table of the hyper-parameters (host rows and their
+    device copy), the bias-correction table and the step counter that :func:`adam_tick` writes, and
+    the slab of the LAMB norms (2 doubles per block, there when some segment has LAMB on)."""
+
+    def __init__(self, seg: SegTables, hyper) -> None:
+        self.seg, self.device = seg, seg.device
+        self.nseg, self.nblocks = seg.nseg, seg.nblocks
+        self.hyper_host = (C.c_float * max(ADAM_HYPER * self.nseg, 1))()
+        self.hyper_dev = self.bias = self.step = self.slab = None
+        self.any_lamb = False
+        if self.device is not None:
+            self.hyper_dev = torch.zeros(len(self.hyper_host), dtype=torch.float32, device=self.device)
+            self.bias = torch.zeros(max(2 * self.nseg, 2), dtype=torch.float32, device=self.device)
+            self.step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.set_hyper(hyper)
+
+    def set_hyper(self, hyper) -> None:
+        """New hyper-parameters for every segment (dicts with ``lr`` and optionally ``betas``,
+        ``eps``, ``weight_decay``, ``lamb``), uploaded in stream order. The values are judged by the
+        launchers, not here. 1 - beta and the low half of each beta are evaluated in double: the
+        kernels never form them from a float beta."""
+        if len(hyper) != self.nseg:
+            raise ValueError(f"adam_tables: {len(hyper)} hyper-parameter rows for {self.nseg} segments")
+        for i, h in enumerate(hyper):
+            unknown = set(h) - set(_ADAM_KEYS)
+            if unknown:
+                raise ValueError(f"adam_tables: unknown hyper-parameter(s) {sorted(unknown)}")
+            b1, b2 = (float(b) for b in h.get("betas", (0.9, 0.999)))
+            row = [float(h["lr"]), b1, b2, float(h.get("eps", 1e-8)), float(h.get("weight_decay", 0.0)),
+                   1.0 if h.get("lamb", False) else 0.0, 1.0 - b1, 1.0 - b2]
+            row += [b - _f32(b) if math.isfinite(b) else 0.0 for b in (b1, b2)]
+            self.hyper_host[ADAM_HYPER * i:ADAM_HYPER * i + len(row)] = row
+        self.any_lamb = any(h.get("lamb", False) for h in hyper)
+        if self.device is not None:
+            if self.nseg:
+                self.hyper_dev.copy_(torch.frombuffer(self.hyper_host, dtype=torch.float32))
+            if self.any_lamb and self.slab is None:
+                self.slab = torch.zeros(max(2 * self.nblocks, 2), dtype=torch.float64, device=self.device)
+
+
+def adam_tables(segments, hyper, device="cuda") -> AdamTables:
+    """Tables of the AdamW / LAMB kernels over ``segments`` (one ``(offset, numel)`` per parameter
+    tensor, cut into SEG_CHUNK blocks as :func:`seg_tables` does); ``hyper``: one dict per segment."""
+    seg, _ = seg_tables(segments, [{"lr": 0.0}] * len(segments), device)
+    return AdamTables(seg, hyper)
+
+
+def _adam_check(rc: int, what: str) -> None:
+    if rc < 0:
+        raise ValueError(f"{what}: {_ADAM_ERRORS.get(rc, f'bad tables ({rc})')}")
+    check(rc, what)
+
+
+def _adam_args(what: str, t: AdamTables, f32: dict, shadow=None, **scalars):
+    """Buffer checks shared by the three update launches; returns the table arguments of the C call."""
+    n = next(iter(f32.values())).numel()
+    _seg_flat(what, n, t.device, shadow=shadow, **f32)
+    if any(x.dtype != torch.float32 for x in f32.values()):
+        raise ValueError(f"{what}: {', '.join(f32)} are f32")
+    if shadow is not None and shadow.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{what}: the shadow is bf16 or fp16")
+    for name, x in scalars.items():
+        if x is not None and (x.device != t.device or x.dtype != torch.float32 or x.numel() < 1):
+            raise ValueError(f"{what}: {name} is a one-element f32 tensor on {t.device}")
+    s = t.seg
+    return (n, ptr(s.seg_dev), ptr(s.blk_dev), C.cast(s.seg_host, C.c_void_p),
+            C.cast(s.blk_host, C.c_void_p), s.nseg, s.nblocks, ptr(t.hyper_dev),
+            C.cast(t.hyper_host, C.c_void_p), ptr(t.bias))
+
+
+def adam_tick(tables: AdamTables, found_inf=None) -> None:
+    """One launch of one block: the device step counter ``tables.step`` advances by one and
+    ``tables.bias`` gets every segment's bias corrections for the new count -- unless ``found_inf``
+    is set, which leaves both as they are."""
+    if tables.device is None or tables.device.type != "cuda":
+        raise ValueError(f"adam_tick runs on a GPU; the tables are on {tables.device}")
+    rc = ext.lib().pda_adam_tick(ptr(tables.hyper_dev), C.cast(tables.hyper_host, C.c_void_p),
+                                 tables.nseg, ptr(tables.step), ptr(tables.bias), ptr(found_inf),
+                                 stream(tables.device))
+    _adam_check(rc, "adam_tick")
+
+
+def adamw_seg(p, g, m, v, shadow, tables: AdamTables, inv_scale=None, found_inf=None) -> None:
+    """The AdamW step of ``torch.optim.AdamW`` (amsgrad off) over the segments of ``tables``, one
+    launch, after :func:`adam_tick`; ``inv_scale`` / ``found_inf`` as in :func:`sgd_seg`. Elements
+    in no segment stay. Bad tables or hyper-parameters raise ValueError and launch nothing."""
+    a = _adam_args("adamw_seg", tables, dict(p=p, g=g, m=m, v=v), shadow, inv_scale=inv_scale,
+                   found_inf=found_inf)
+    rc = ext.lib().pda_adamw_seg(ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), *a, ptr(inv_scale),
+                                 ptr(found_inf), 2 if shadow is not None else 0,
+                                 dt_of(shadow) if shadow is not None else 1, stream(p.device))
+    _adam_check(rc, "adamw_seg")
+
+
+def lamb_moments(p, g, m, v, tables: AdamTables, inv_scale=None, found_inf=None) -> None:
+    """LAMB, phase A (after :func:`adam_tick`): m and v updated, and per block the double sums of
+    p^2 and u^2 of the segments with LAMB on into ``tables.slab``."""
+    a = _adam_args("lamb_moments", tables, dict(p=p, g=g, m=m, v=v), inv_scale=inv_scale,
+                   found_inf=found_inf)
+    rc = ext.lib().pda_lamb_moments(ptr(p), ptr(g), ptr(m), ptr(v), *a, ptr(tables.slab),
+                                    ptr(inv_scale), ptr(found_inf), stream(p.device))
+    _adam_check(rc, "lamb_moments")
+
+
+def lamb_apply(p, m, v, shadow, tables: AdamTables, found_inf=None) -> None:
+    """LAMB, phase B: the trust ratios from ``tables.slab``, then p (and the shadow) of every
+    segment; segments with LAMB off step with ratio 1."""
+    a = _adam_args("lamb_apply", tables, dict(p=p, m=m, v=v), shadow, found_inf=found_inf)
+    rc = ext.lib().pda_lamb_apply(ptr(p), ptr(m), ptr(v), ptr(shadow), *a, ptr(tables.slab),
+                                  ptr(found_inf), 2 if shadow is not None else 0,
+                                  dt_of(shadow) if shadow is not None else 1, stream(p.device))
+    _adam_check(rc, "lamb_apply")
 
 
 # ------------------------------------------------------------------ gradient clipping (csrc/clip.hip)

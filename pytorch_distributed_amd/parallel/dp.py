@@ -188,12 +188,17 @@ class DataParallel(nn.Module):
         self._refuse_clip(kw.get("clip_grad_norm", 0.0))
         if self._native:
             from ..models.native import NativeSGD
-            self._refuse_segmented(NativeSGD.wants_segments(**kw))
+            # (AdamW / LAMB keep their hyper-parameters in a device table too: always segmented)
+            self._refuse_segmented(kw.get("opt", "sgd") != "sgd" or NativeSGD.wants_segments(**kw))
             opts = [m.make_optimizer(**kw) for m in self.all_modules]
             return ReplicatedSGD(opts) if self.replicas else opts[0]
         kw.pop("clip_grad_norm", None)       # (torch optimizers: the trainer clips before step())
         groups = kw.pop("param_groups", None)
         params = groups if groups is not None else self.module.parameters()
+        opt = kw.pop("opt", "sgd")
+        if opt != "sgd":
+            from ..optim import LAMB
+            return LAMB(params, **kw) if opt == "lamb" else torch.optim.AdamW(params, **kw)
         if kw.get("lars", 0) > 0 or any(g.get("lars", 0) > 0 for g in groups or []):
             from ..optim import LARS
             return LARS(params, **kw)

@@ -133,14 +133,15 @@ def graphs_unsafe_warning(what: str) -> None:
 
 
 # Captured steps bake the learning rate into the optimizer launch and re-capture when it changes;
-# the segmented optimizer (parameter groups, Nesterov, LARS: models/native.py NativeSGD.segmented)
-# keeps its hyper-parameters in a device table that is re-uploaded between steps, which a replayed
-# graph would not see. It is refused there, with no fall-back to eager launches.
-SEGMENTED_REFUSAL = ("{what} cannot run the segmented optimizer (parameter groups, Nesterov or LARS): "
-                     "captured steps (MX_GRAPH=1, the DataParallel replica graphs) take their "
+# the segmented optimizer (parameter groups, Nesterov, LARS: models/native.py NativeSGD.segmented;
+# AdamW and LAMB: NativeAdamW, always) keeps its hyper-parameters in a device table that is
+# re-uploaded between steps, which a replayed graph would not see. It is refused there, with no
+# fall-back to eager launches.
+SEGMENTED_REFUSAL = ("{what} cannot run the segmented optimizer (parameter groups, Nesterov, LARS, "
+                     "AdamW or LAMB): captured steps (MX_GRAPH=1, the DataParallel replica graphs) take their "
                      "hyper-parameters at capture. Run without MX_GRAPH / on one device without "
                      "DataParallel's replay (the single-GPU and DDP scripts work), or drop "
-                     "MX_NESTEROV / MX_NO_BN_DECAY / MX_LARS / param_groups")
+                     "MX_NESTEROV / MX_NO_BN_DECAY / MX_LARS / MX_OPT / param_groups")
 
 
 # Gradient clipping (MX_CLIP_GRAD_NORM) lives inside NativeSGD.step(), so MX_GRAPH=1 captures it; the

@@ -396,7 +396,11 @@ def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
     torch engine. The captured-step paths refuse the segmented optimizer (ValueError, raised here:
     before training starts). ``MX_CLIP_GRAD_NORM`` goes to the native optimizer, which clips inside
     its step; the torch optimizers are clipped by :func:`train`. DataParallel over several devices
-    (or with ``PDA_DP_FORCE_REPLAY=1``) refuses it, here as well."""
+    (or with ``PDA_DP_FORCE_REPLAY=1``) refuses it, here as well. ``MX_OPT=adamw|lamb`` builds the
+    adaptive optimizers instead (``MX_BETAS``, ``MX_OPT_EPS``, ``MX_WEIGHT_DECAY``; LAMB's trust ratio
+    on tensors with ``dim() >= 2``): the native AdamW / LAMB kernels, which the captured-step paths
+    refuse like the segmented SGD, or ``torch.optim.AdamW`` /
+    :class:`~pytorch_distributed_amd.optim.LAMB` on the torch engine."""
     inner = _factory_owner(model, "make_optimizer")
     native = hasattr(inner, "make_optimizer")
     clip = {}
@@ -405,6 +409,17 @@ def build_optimizer(cfg: RunConfig, model: nn.Module, ctx: Context):
         if replays_captured_steps(model):
             raise ValueError(CLIP_REFUSAL.format(what=DP_REPLAY))
         clip = dict(clip_grad_norm=cfg.clip_grad_norm)
+    if cfg.opt != "sgd":
+        from .optim import LAMB, build_param_groups
+        if native and cfg.graph and ctx.engine == "native":
+            from .runtime.graphs import SEGMENTED_REFUSAL
+            raise ValueError(SEGMENTED_REFUSAL.format(what="MX_GRAPH=1"))
+        groups = build_param_groups(_unwrap(model), cfg.weight_decay, cfg.no_bn_decay,
+                                    lamb=cfg.opt == "lamb")
+        kw = dict(lr=cfg.lr, betas=cfg.betas, eps=cfg.opt_eps, weight_decay=cfg.weight_decay)
+        if native:      # (DataParallel over several devices raises the same ValueError)
+            return inner.make_optimizer(opt=cfg.opt, param_groups=groups, **kw, **clip)
+        return LAMB(groups, **kw) if cfg.opt == "lamb" else torch.optim.AdamW(groups, **kw)
     if not (cfg.nesterov or cfg.no_bn_decay or cfg.lars > 0):
         if native:
             return inner.make_optimizer(lr=cfg.lr, momentum=cfg.momentum,
