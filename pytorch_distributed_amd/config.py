@@ -61,6 +61,7 @@ class RunConfig:
     ema_warmup: bool = True          # EMA decay min(decay, (1 + t) / (10 + t)) over its updates t
     clip_grad_norm: float = 0.0      # maximum global L2 norm of the gradient (0 = off)
     random_erase: float = 0.0        # random-erasing probability p in [0, 1] (0 = off)
+    color_jitter: tuple = (0.0, 0.0, 0.0, 0.0)   # ColorJitter strengths (brightness, contrast, saturation, hue)
     opt: str = "sgd"                 # sgd | adamw | lamb
     betas: tuple = (0.9, 0.999)      # AdamW / LAMB moment decays b1, b2 in [0, 1)
     opt_eps: float = 1e-8            # AdamW / LAMB eps
@@ -91,6 +92,17 @@ def _betas(s: str) -> tuple:
     if len(b) != 2:
         raise ValueError(f"MX_BETAS is 'b1,b2', got {s!r}")
     return b
+
+
+def _color_jitter(s: str) -> tuple:
+    """``v`` = (v, v, v, 0) (timm's ``color_jitter=v``), ``b,c,s`` or ``b,c,s,h``."""
+    try:
+        v = tuple(float(x) for x in s.split(","))
+    except ValueError:
+        v = ()
+    if len(v) not in (1, 3, 4):
+        raise ValueError(f"MX_COLOR_JITTER is 'v', 'b,c,s' or 'b,c,s,h', got {s!r}")
+    return v * 3 + (0.0,) if len(v) == 1 else v + (0.0,) * (4 - len(v))
 
 
 _ENV = {
@@ -130,6 +142,7 @@ _ENV = {
     "MX_EMA_WARMUP": ("ema_warmup", _bool),
     "MX_CLIP_GRAD_NORM": ("clip_grad_norm", float),
     "MX_RANDOM_ERASE": ("random_erase", float),
+    "MX_COLOR_JITTER": ("color_jitter", _color_jitter),
     "MX_OPT": ("opt", str),
     "MX_BETAS": ("betas", _betas),
     "MX_OPT_EPS": ("opt_eps", float),
@@ -194,6 +207,10 @@ def config_for(script: str, env: Optional[dict] = None,
     if not 0 <= cfg.random_erase <= 1:
         raise ValueError(f"MX_RANDOM_ERASE is a probability in [0, 1] (0 = off), got "
                          f"{cfg.random_erase!r}")
+    b, c, s, h = cfg.color_jitter
+    if not (0 <= b < float("inf") and 0 <= c < float("inf") and 0 <= s < float("inf") and 0 <= h <= 0.5):
+        raise ValueError(f"MX_COLOR_JITTER: brightness, contrast and saturation are finite and >= 0, "
+                         f"hue lies in [0, 0.5] (all 0 = off), got {cfg.color_jitter!r}")
     if cfg.opt not in ("sgd", "adamw", "lamb"):
         raise ValueError(f"MX_OPT must be sgd|adamw|lamb, got {cfg.opt!r}")
     if not all(0 <= b < 1 for b in cfg.betas):

@@ -391,6 +391,34 @@ int pda_erase_draw(int B, int S, unsigned bkey, double p, double s0, double s1, 
 int pda_batch_erase(void* x, const int* boxes, int B, int S, int dt, int layout, int grid_cap,
                     hipStream_t st);
 
+// ------------------------------------------------------------------ jitter.hip
+// Colour-jitter table of a batch of B samples, one launch on stream st: table (device int32 [B][5],
+// 4-byte aligned) row n = the bits of the float32 factors (brightness, contrast, saturation, hue) and
+// the op order in nibbles (nibble k = the op at position k: 0 brightness, 1 contrast, 2 saturation,
+// 3 hue, 15 = skipped). bkey: the batch's key (jitter.py batch_key); b, c, s, h: the strengths, an
+// op of strength 0 is skipped. Returns -2 and launches nothing for B <= 0, a non-finite strength,
+// b, c or s < 0, h outside [0, 0.5], or a null or misaligned table.
+int pda_jitter_draw(int B, unsigned bkey, double b, double c, double s, double h, int* table,
+                    hipStream_t st);
+// Partial sums per sample that pda_jitter_mean writes for these arguments (the slab holds B times as
+// many doubles), at most 64; -2 for arguments pda_batch_erase refuses.
+int pda_jitter_bps(int B, int S, int dt, int layout, int grid_cap);
+// The contrast mean's partial sums: slab (device doubles, 8-byte aligned, slab_len of them, at least
+// B * pda_jitter_bps) row n = the per-block sums of gray over sample n as it stands when contrast is
+// reached (0 for a sample whose row has no contrast). x, layouts, dtypes and grid_cap as
+// pda_batch_erase; mean, stdev: the normalisation, 3 host floats each (stdev > 0). Returns -2 for
+// what pda_batch_erase refuses, a null or misaligned table or slab, or a slab that is too small.
+int pda_jitter_mean(const void* x, const int* table, double* slab, long long slab_len, int B, int S,
+                    int dt, int layout, const float* mean, const float* stdev, int grid_cap,
+                    hipStream_t st);
+// x (in place) = normalise(ops(clamp(x * stdev + mean, 0, 1))), the ops and factors of each sample's
+// table row in the row's order. with_mean: pda_jitter_mean ran before with the same B, S, dt, layout
+// and grid_cap; 0: slab is not read and a contrast op in the table is skipped. The s2d padding slots
+// keep their bits. Returns -2 as pda_jitter_mean (the slab is checked when with_mean is set).
+int pda_batch_jitter(void* x, const int* table, const double* slab, long long slab_len, int with_mean,
+                     int B, int S, int dt, int layout, const float* mean, const float* stdev,
+                     int grid_cap, hipStream_t st);
+
 // ------------------------------------------------------------------ ema.hip
 // Host-side validation of a range table. 0 = good; otherwise the negative code that
 // ops/native_ops.py turns into a ValueError:

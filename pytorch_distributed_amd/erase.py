@@ -41,13 +41,19 @@ def _hash32(x: int) -> int:
     return x
 
 
-def batch_key(seed: int, rank: int, epoch: int, step: int) -> int:
+def batch_key(seed: int, rank: int, epoch: int, step: int, stream: int = _STREAM) -> int:
     """The uint32 key of one batch's draws: four nested hashes, so changing any one of the four
-    arguments changes every box. Computed on the host and handed to the kernel."""
-    k = _hash32(int(seed) * 97 + _STREAM)
+    arguments changes every box. Computed on the host and handed to the kernel. ``stream`` keeps
+    the draws of another per-batch transform (``jitter.py``) apart from these."""
+    k = _hash32(int(seed) * 97 + stream)
     for v in (rank, epoch, step):
         k = _hash32(k ^ (int(v) & _M32))
     return k
+
+
+def _subkey(bkey: int, b: int) -> int:
+    """csrc/batch_image.h counter_subkey: the key of the sample at batch position b."""
+    return _hash32(bkey ^ ((b * 0x9E3779B9 + 0x85EBCA6B) & _M32))
 
 
 def _uniform(skey: int, k: int) -> float:
@@ -80,7 +86,7 @@ def draw_erase(seed: int, rank: int, epoch: int, step: int, B: int, S: int, p: f
     boxes = np.zeros((B, 4), dtype=np.int32)
     full = float(S) * float(S)
     for b in range(B):
-        skey = _hash32(bkey ^ ((b * 0x9E3779B9 + 0x85EBCA6B) & _M32))
+        skey = _subkey(bkey, b)
         if not _uniform(skey, 0) < p:
             continue
         for a in range(ATTEMPTS):

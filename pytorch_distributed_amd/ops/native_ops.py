@@ -34,6 +34,7 @@ __all__ = [
     "ADAM_HYPER", "AdamTables", "adam_tables", "adam_tick", "adamw_seg", "lamb_moments", "lamb_apply",
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
     "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
+    "jitter_strengths", "jitter_draw", "jitter_bps", "batch_jitter", "batch_jitter_check",
 ]
 
 
@@ -1962,6 +1963,91 @@ def batch_erase(x, boxes, layout: int) -> None:
         raise ValueError("batch_erase: x must be 16-byte aligned (boxes 4-byte)")
     check(ext.lib().pda_batch_erase(ptr(x), ptr(boxes), B, S, dt_of(x), layout, 0, stream(x.device)),
           "batch_erase")
+
+
+# ------------------------------------------------------------------ colour jitter of a batch
+def jitter_strengths(strengths) -> Tuple[float, float, float, float]:
+    """``(b, c, s, h)`` of a colour jitter, validated as ``pda_jitter_draw`` takes them: finite,
+    brightness, contrast and saturation >= 0, hue in [0, 0.5]; 0 switches an op off."""
+    v = tuple(float(x) for x in strengths)
+    if len(v) != 4 or not all(math.isfinite(x) and x >= 0 for x in v) or v[3] > 0.5:
+        raise ValueError(f"jitter_draw: strengths (brightness, contrast, saturation, hue) must be "
+                         f"finite and >= 0, hue at most 0.5, got {strengths!r}")
+    return v
+
+
+def _jitter_table_check(what: str, table, B: Optional[int] = None) -> int:
+    if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 5 or not table.is_contiguous():
+        raise ValueError(f"{what}: the table must be a contiguous int32 [B, 5] tensor, got "
+                         f"{tuple(table.shape)} {table.dtype}")
+    if table.shape[0] < 1 or (B is not None and table.shape[0] != B):
+        raise ValueError(f"{what}: the table has {table.shape[0]} rows for a batch of "
+                         f"{B if B is not None else '>= 1'}")
+    return table.shape[0]
+
+
+def jitter_draw(table, bkey: int, strengths) -> None:
+    """Draw the colour-jitter table of a batch on the device (one launch, csrc/jitter.hip
+    ``jitter_draw_kernel``) into ``table``, a device int32 [B, 5] tensor (``jitter.jitter_table``'s
+    packing). ``bkey``: ``jitter.batch_key(seed, rank, epoch, step)``; ``jitter.draw_jitter`` is the
+    host mirror."""
+    B = _jitter_table_check("jitter_draw", table)
+    b, c, s, h = jitter_strengths(strengths)
+    if table.device.type != "cuda":
+        raise ValueError("jitter_draw runs on a GPU; the table is on " + str(table.device))
+    if table.data_ptr() % 4:
+        raise ValueError("jitter_draw: the table must be 4-byte aligned")
+    check(ext.lib().pda_jitter_draw(B, int(bkey) & 0xFFFFFFFF, b, c, s, h, ptr(table),
+                                    stream(table.device)), "jitter_draw")
+
+
+def jitter_bps(B: int, S: int, dtype, layout: int, grid_cap: int = 0) -> int:
+    """Partial sums per sample of the contrast-mean pass: :func:`batch_jitter`'s slab holds
+    ``B * jitter_bps(...)`` doubles."""
+    n = ext.lib().pda_jitter_bps(int(B), int(S), ext.DT[dtype], layout, grid_cap)
+    if n < 1:
+        raise ValueError(f"jitter_bps: no {S}x{S} batch of {B} in layout {layout}, {dtype}")
+    return n
+
+
+def batch_jitter_check(x, table, layout: int, slab=None) -> Tuple[int, int]:
+    """Host-side validation of a :func:`batch_jitter` call; returns (B, S). Pure Python (the kernel
+    library is not loaded), run before the launches. The table's VALUES are not read: the kernel
+    skips every nibble that names no op."""
+    B, S = batch_shape("batch_jitter", x, layout)
+    _jitter_table_check("batch_jitter", table, B)
+    if table.device != x.device or (slab is not None and slab.device != x.device):
+        raise ValueError(f"batch_jitter: the table and the slab must be on the batch's {x.device}")
+    if slab is not None and (slab.dtype != torch.float64 or slab.dim() != 1 or not slab.is_contiguous()):
+        raise ValueError(f"batch_jitter: the slab must be a contiguous 1-D float64 tensor, got "
+                         f"{tuple(slab.shape)} {slab.dtype}")
+    return B, S
+
+
+def batch_jitter(x, table, layout: int, slab=None, grid_cap: int = 0) -> None:
+    """Colour-jitter a finished batch in place (csrc/jitter.hip): per sample, the ops and float32
+    factors of its ``table`` row (device int32 [B, 5], as :func:`jitter_draw` writes it) in the row's
+    order, between un-normalising and re-normalising with ``data/synthetic.py``'s MEAN and STD.
+    ``layout``: ``AUG_S2D`` [B, S/2, S/2, 16] (f32 / bf16 / f16) or ``AUG_NCHW`` [B, 3, S, S] f32.
+    ``slab``: ``B * jitter_bps(B, S, x.dtype, layout, grid_cap)`` device doubles for the contrast
+    mean, which then costs a launch of its own before the apply; None: no mean is taken and a
+    contrast op in the table is skipped. The s2d padding slots keep their bits."""
+    from ..data.synthetic import MEAN, STD
+    B, S = batch_jitter_check(x, table, layout, slab)
+    if x.device.type != "cuda":
+        raise ValueError("batch_jitter runs on a GPU; the batch is on " + str(x.device))
+    if x.data_ptr() % 16 or table.data_ptr() % 4 or (slab is not None and slab.data_ptr() % 8):
+        raise ValueError("batch_jitter: x must be 16-byte aligned (the table 4-byte, the slab 8-byte)")
+    if slab is not None and slab.numel() < B * jitter_bps(B, S, x.dtype, layout, grid_cap):
+        raise ValueError(f"batch_jitter: a slab of {slab.numel()} doubles, the mean pass writes "
+                         f"{B * jitter_bps(B, S, x.dtype, layout, grid_cap)}")
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    L, n = ext.lib(), 0 if slab is None else slab.numel()
+    if slab is not None:
+        check(L.pda_jitter_mean(ptr(x), ptr(table), ptr(slab), n, B, S, dt_of(x), layout, mean, std,
+                                grid_cap, stream(x.device)), "jitter_mean")
+    check(L.pda_batch_jitter(ptr(x), ptr(table), ptr(slab), n, int(slab is not None), B, S, dt_of(x),
+                             layout, mean, std, grid_cap, stream(x.device)), "batch_jitter")
 
 
 AUG_TRAIN, AUG_VAL = 0, 1

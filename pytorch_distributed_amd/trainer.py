@@ -157,6 +157,18 @@ def _batch_eraser(ctx: Context):
     return eraser
 
 
+def _batch_jitter(ctx: Context):
+    """``MX_COLOR_JITTER``: the run's :class:`~pytorch_distributed_amd.jitter.BatchJitter` (kept on
+    the context: one table and one slab serve every epoch), else None."""
+    if not any(v > 0 for v in ctx.cfg.color_jitter):
+        return None
+    jitter = ctx.extra.get("jitter")
+    if jitter is None:
+        from .jitter import BatchJitter
+        jitter = ctx.extra["jitter"] = BatchJitter(ctx.cfg, ctx)
+    return jitter
+
+
 def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: Context,
           start_step: int, best_acc: float, save_path: Path) -> int:
     """One epoch of training (reference ``restnet_ddp.py:19-47``). Returns steps run."""
@@ -167,6 +179,7 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     soft = cfg.soft_targets
     mixer = _batch_mixer(ctx)
     eraser = _batch_eraser(ctx)
+    jitter = _batch_jitter(ctx)
     from .utils.metrics import StepProfiler
     prof = StepProfiler(int(os.environ.get("MX_PROFILE", "0") or 0) if epoch == 0 else 0, save_path,
                         ctx.rank)
@@ -187,6 +200,10 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             sb.begin()
         samples = samples.to(ctx.device, non_blocking=True)
         labels = labels.to(ctx.device, non_blocking=True)
+        if jitter is not None:
+            # photometric first, as a transform pipeline orders it: the erase writes the mean colour
+            # (0) into a picture that already has its colours; in place, like the erase below
+            samples = jitter(samples, epoch, step)
         if eraser is not None:
             # per-sample transform, so before the mixing (torchvision's order); in place: every
             # loader makes a fresh batch per step, and the captured steps (MX_GRAPH=1, DataParallel)
