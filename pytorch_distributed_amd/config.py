@@ -62,6 +62,7 @@ class RunConfig:
     clip_grad_norm: float = 0.0      # maximum global L2 norm of the gradient (0 = off)
     random_erase: float = 0.0        # random-erasing probability p in [0, 1] (0 = off)
     color_jitter: tuple = (0.0, 0.0, 0.0, 0.0)   # ColorJitter strengths (brightness, contrast, saturation, hue)
+    rand_augment: tuple = (0, 0)     # RandAugment (n ops in 0..4, magnitude bin m in 0..30); n = 0: off
     opt: str = "sgd"                 # sgd | adamw | lamb
     betas: tuple = (0.9, 0.999)      # AdamW / LAMB moment decays b1, b2 in [0, 1)
     opt_eps: float = 1e-8            # AdamW / LAMB eps
@@ -105,6 +106,18 @@ def _color_jitter(s: str) -> tuple:
     return v * 3 + (0.0,) if len(v) == 1 else v + (0.0,) * (4 - len(v))
 
 
+def _rand_augment(s: str) -> tuple:
+    """``n,m``: n ops per sample (0..4, 0 = off) of magnitude bin m (0..30)."""
+    try:
+        v = tuple(int(x) for x in s.split(","))
+    except ValueError:
+        v = ()
+    if len(v) != 2 or not (0 <= v[0] <= 4 and 0 <= v[1] <= 30):
+        raise ValueError(f"MX_RAND_AUGMENT is 'n,m' with integers n in 0..4 (0 = off) and m in 0..30, "
+                         f"got {s!r}")
+    return v
+
+
 _ENV = {
     "MX_EPOCHS": ("epochs", int),
     "MX_BATCH": ("batch_size", int),
@@ -143,6 +156,7 @@ _ENV = {
     "MX_CLIP_GRAD_NORM": ("clip_grad_norm", float),
     "MX_RANDOM_ERASE": ("random_erase", float),
     "MX_COLOR_JITTER": ("color_jitter", _color_jitter),
+    "MX_RAND_AUGMENT": ("rand_augment", _rand_augment),
     "MX_OPT": ("opt", str),
     "MX_BETAS": ("betas", _betas),
     "MX_OPT_EPS": ("opt_eps", float),

@@ -419,6 +419,42 @@ int pda_batch_jitter(void* x, const int* table, const double* slab, long long sl
                      int B, int S, int dt, int layout, const float* mean, const float* stdev,
                      int grid_cap, hipStream_t st);
 
+// ------------------------------------------------------------------ randaug.hip
+// int32 per sample and slot of the statistics table (3 x 256 histogram counts, 3 min codes, 3 max
+// bits, 2 unused): the table holds n * B rows of it, slot-major, 16-byte aligned.
+int pda_randaug_stat_row();
+// RandAugment table of a batch of B SxS samples, n ops of magnitude bin m each, one launch on stream
+// st: table (device int32 [B][n][8], 4-byte aligned) row (b, j) = the op id (0 Identity, 1 / 2 ShearX /
+// ShearY, 3 / 4 TranslateX / TranslateY, 5 Rotate, 6 Brightness, 7 Color, 8 Contrast, 9 Sharpness,
+// 10 Posterize, 11 Solarize, 12 AutoContrast, 13 Equalize), the bits of the float32 factor or
+// threshold (the posterize mask as an integer), and the bits of six float32 affine coefficients (0
+// for a non-geometric op). The rows of stats (stats_len int32) that the drawn ops accumulate into are
+// zeroed. bkey: the batch's key (randaug.py batch_key). Returns -2 and launches nothing for B <= 0,
+// n outside 1..4, m outside 0..30, S outside 1..32768, a null or misaligned table or stats, or a
+// stats table below n * B * pda_randaug_stat_row().
+int pda_randaug_draw(int B, int n, int m, int S, unsigned bkey, int* table, int* stats,
+                     long long stats_len, hipStream_t st);
+// Partial sums per sample that pda_randaug_stats writes for these arguments (the slab holds B times
+// as many doubles), at most 64; -2 for arguments pda_batch_erase refuses.
+int pda_randaug_bps(int B, int S, int dt, int layout, int grid_cap);
+// The statistics of slot `slot` over x, for the samples whose op there needs them: Equalize the
+// per-channel histogram of floor(255 x01 + 0.5) and AutoContrast the per-channel min / max, added by
+// integer atomics into the slot's ZEROED rows of stats; Contrast the per-block sums of gray into
+// slab (device doubles, 8-byte aligned, at least B * pda_randaug_bps). x, layouts, dtypes and
+// grid_cap as pda_batch_erase; mean, stdev: the normalisation, 3 host floats each (stdev > 0).
+// Returns -2 for what pda_batch_erase refuses, n outside 1..4, slot outside 0..n-1, a null or
+// misaligned table, stats or slab, or a stats table or slab that is too small.
+int pda_randaug_stats(const void* x, const int* table, int n, int slot, int* stats, long long stats_len,
+                      double* slab, long long slab_len, int B, int S, int dt, int layout,
+                      const float* mean, const float* stdev, int grid_cap, hipStream_t st);
+// dst = slot `slot` of every sample's table row applied to src (un-normalise, the op, re-normalise,
+// one rounding to dt; a geometric op copies stored values or writes 0), after pda_randaug_stats with
+// the same arguments; the s2d padding slots of dst get src's bits. Returns -2 as pda_randaug_stats,
+// and for src and dst that overlap: a slot cannot run in place.
+int pda_randaug_apply(const void* src, void* dst, const int* table, int n, int slot, const int* stats,
+                      long long stats_len, const double* slab, long long slab_len, int B, int S, int dt,
+                      int layout, const float* mean, const float* stdev, int grid_cap, hipStream_t st);
+
 // ------------------------------------------------------------------ ema.hip
 // Host-side validation of a range table. 0 = good; otherwise the negative code that
 // ops/native_ops.py turns into a ValueError:

@@ -35,6 +35,7 @@ __all__ = [
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
     "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
     "jitter_strengths", "jitter_draw", "jitter_bps", "batch_jitter", "batch_jitter_check",
+    "randaug_stat_row", "randaug_check", "randaug_draw", "randaug_bps", "randaug_stats", "randaug_apply",
 ]
 
 
@@ -2048,6 +2049,111 @@ def batch_jitter(x, table, layout: int, slab=None, grid_cap: int = 0) -> None:
                                 grid_cap, stream(x.device)), "jitter_mean")
     check(L.pda_batch_jitter(ptr(x), ptr(table), ptr(slab), n, int(slab is not None), B, S, dt_of(x),
                              layout, mean, std, grid_cap, stream(x.device)), "batch_jitter")
+
+
+# ------------------------------------------------------------------ RandAugment of a batch
+def randaug_stat_row() -> int:
+    """int32 per sample and slot of the statistics table (csrc/randaug.hip STAT_ROW)."""
+    return ext.lib().pda_randaug_stat_row()
+
+
+def randaug_bps(B: int, S: int, dtype, layout: int, grid_cap: int = 0) -> int:
+    """Partial sums per sample of a Contrast slot's gray sum: the slab of :func:`randaug_stats` /
+    :func:`randaug_apply` holds ``B * randaug_bps(...)`` doubles."""
+    n = ext.lib().pda_randaug_bps(int(B), int(S), ext.DT[dtype], layout, grid_cap)
+    if n < 1:
+        raise ValueError(f"randaug_bps: no {S}x{S} batch of {B} in layout {layout}, {dtype}")
+    return n
+
+
+def randaug_check(what: str, table, stats, slab=None, B: Optional[int] = None) -> Tuple[int, int]:
+    """Host-side validation of the tables of a RandAugment launch; returns (B, n). ``table``: int32
+    [B, n, 8] with n in 1..4; ``stats``: flat int32, ``n * B * randaug_stat_row()`` at least (checked
+    by the launcher); ``slab``: flat float64. Pure Python."""
+    if (table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != 8 or not table.is_contiguous()
+            or not 1 <= table.shape[1] <= 4 or table.shape[0] < 1 or (B is not None and table.shape[0] != B)):
+        raise ValueError(f"{what}: the table must be a contiguous int32 [B, n, 8] tensor, n in 1..4, of "
+                         f"{B if B is not None else '>= 1'} samples, got {tuple(table.shape)} {table.dtype}")
+    if stats.dtype != torch.int32 or stats.dim() != 1 or not stats.is_contiguous() or stats.device != table.device:
+        raise ValueError(f"{what}: the statistics table must be a contiguous 1-D int32 tensor on the "
+                         f"table's {table.device}, got {tuple(stats.shape)} {stats.dtype} {stats.device}")
+    if slab is not None and (slab.dtype != torch.float64 or slab.dim() != 1 or not slab.is_contiguous()
+                             or slab.device != table.device):
+        raise ValueError(f"{what}: the slab must be a contiguous 1-D float64 tensor on the table's "
+                         f"{table.device}, got {tuple(slab.shape)} {slab.dtype} {slab.device}")
+    return table.shape[0], table.shape[1]
+
+
+def randaug_draw(table, stats, S: int, bkey: int, m: int) -> None:
+    """Draw the RandAugment table of a batch on the device (one launch, csrc/randaug.hip
+    ``randaug_draw_kernel``) into ``table``, a device int32 [B, n, 8] tensor (``randaug.pack_table``'s
+    packing), n ops of magnitude bin ``m`` (0..30) per sample, and zero the rows of ``stats`` the
+    drawn ops accumulate into. ``bkey``: ``randaug.batch_key(seed, rank, epoch, step)``;
+    ``randaug.draw_randaug`` is the host mirror."""
+    B, n = randaug_check("randaug_draw", table, stats)
+    if int(m) != m or not 0 <= m <= 30:
+        raise ValueError(f"randaug_draw: the magnitude bin {m!r} lies outside 0..30")
+    if int(S) != S or not 1 <= S <= AUG_MAX_SIDE:
+        raise ValueError(f"randaug_draw: image side {S!r} outside 1..{AUG_MAX_SIDE}")
+    if table.device.type != "cuda":
+        raise ValueError("randaug_draw runs on a GPU; the table is on " + str(table.device))
+    if table.data_ptr() % 4 or stats.data_ptr() % 16 or stats.numel() < n * B * randaug_stat_row():
+        raise ValueError(f"randaug_draw: the table must be 4-byte and the statistics table 16-byte aligned, "
+                         f"with {n * B * randaug_stat_row()} int32 at least, got {stats.numel()}")
+    check(ext.lib().pda_randaug_draw(B, n, int(m), int(S), int(bkey) & 0xFFFFFFFF, ptr(table), ptr(stats),
+                                     stats.numel(), stream(table.device)), "randaug_draw")
+
+
+def _randaug_slot(what: str, x, table, slot: int, stats, slab, layout: int, grid_cap: int):
+    B, S = batch_shape(what, x, layout)
+    _, n = randaug_check(what, table, stats, slab, B)
+    if table.device != x.device:
+        raise ValueError(f"{what}: the tables must be on the batch's {x.device}")
+    if int(slot) != slot or not 0 <= slot < n:
+        raise ValueError(f"{what}: slot {slot!r} of a table of {n} slots")
+    if x.device.type != "cuda":
+        raise ValueError(f"{what} runs on a GPU; the batch is on {x.device}")
+    if x.data_ptr() % 16 or table.data_ptr() % 4 or stats.data_ptr() % 16 or slab.data_ptr() % 8:
+        raise ValueError(f"{what}: the batch and the statistics table must be 16-byte aligned (the "
+                         f"table 4-byte, the slab 8-byte)")
+    if stats.numel() < n * B * randaug_stat_row() or slab.numel() < B * randaug_bps(B, S, x.dtype, layout, grid_cap):
+        raise ValueError(f"{what}: a statistics table of {stats.numel()} int32 and a slab of {slab.numel()} "
+                         f"doubles, the launches need {n * B * randaug_stat_row()} and "
+                         f"{B * randaug_bps(B, S, x.dtype, layout, grid_cap)}")
+    return B, S, n
+
+
+def randaug_stats(x, table, slot: int, stats, slab, layout: int, grid_cap: int = 0) -> None:
+    """The statistics of slot ``slot`` over the batch ``x`` (one launch, csrc/randaug.hip): for the
+    samples whose op there is Equalize or AutoContrast, the histogram or min / max into the slot's
+    rows of ``stats`` (zeroed before, as :func:`randaug_draw` leaves them); for Contrast the gray
+    sums into ``slab``. Every other sample's blocks return at once."""
+    from ..data.synthetic import MEAN, STD
+    B, S, n = _randaug_slot("randaug_stats", x, table, slot, stats, slab, layout, grid_cap)
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    check(ext.lib().pda_randaug_stats(ptr(x), ptr(table), n, int(slot), ptr(stats), stats.numel(), ptr(slab),
+                                      slab.numel(), B, S, dt_of(x), layout, mean, std, grid_cap,
+                                      stream(x.device)), "randaug_stats")
+
+
+def randaug_apply(src, dst, table, slot: int, stats, slab, layout: int, grid_cap: int = 0) -> None:
+    """``dst`` = slot ``slot`` of every sample's ``table`` row applied to ``src`` (one launch,
+    csrc/randaug.hip), after :func:`randaug_stats` with the same arguments. ``layout``: ``AUG_S2D``
+    [B, S/2, S/2, 16] (f32 / bf16 / f16) or ``AUG_NCHW`` [B, 3, S, S] f32. Out of place: the geometric
+    ops gather and Sharpness reads a neighbourhood. The s2d padding slots of ``dst`` get ``src``'s."""
+    from ..data.synthetic import MEAN, STD
+    B, S, n = _randaug_slot("randaug_apply", src, table, slot, stats, slab, layout, grid_cap)
+    if (dst.shape != src.shape or dst.dtype != src.dtype or dst.device != src.device
+            or not dst.is_contiguous() or dst.data_ptr() % 16):
+        raise ValueError(f"randaug_apply: dst must be contiguous, 16-byte aligned and have the shape, dtype "
+                         f"and device of src, got {tuple(dst.shape)} {dst.dtype} {dst.device}")
+    nbytes = src.numel() * src.element_size()
+    if src.data_ptr() < dst.data_ptr() + nbytes and dst.data_ptr() < src.data_ptr() + nbytes:
+        raise ValueError("randaug_apply: dst overlaps src (a slot gathers: it runs out of place)")
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    check(ext.lib().pda_randaug_apply(ptr(src), ptr(dst), ptr(table), n, int(slot), ptr(stats), stats.numel(),
+                                      ptr(slab), slab.numel(), B, S, dt_of(src), layout, mean, std, grid_cap,
+                                      stream(src.device)), "randaug_apply")
 
 
 AUG_TRAIN, AUG_VAL = 0, 1

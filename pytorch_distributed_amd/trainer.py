@@ -169,6 +169,18 @@ def _batch_jitter(ctx: Context):
     return jitter
 
 
+def _batch_randaug(ctx: Context):
+    """``MX_RAND_AUGMENT``: the run's :class:`~pytorch_distributed_amd.randaug.BatchRandAugment` (kept
+    on the context: its tables, slab and second buffer serve every epoch), else None."""
+    if not ctx.cfg.rand_augment[0] > 0:
+        return None
+    randaug = ctx.extra.get("randaug")
+    if randaug is None:
+        from .randaug import BatchRandAugment
+        randaug = ctx.extra["randaug"] = BatchRandAugment(ctx.cfg, ctx)
+    return randaug
+
+
 def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: Context,
           start_step: int, best_acc: float, save_path: Path) -> int:
     """One epoch of training (reference ``restnet_ddp.py:19-47``). Returns steps run."""
@@ -180,6 +192,7 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     mixer = _batch_mixer(ctx)
     eraser = _batch_eraser(ctx)
     jitter = _batch_jitter(ctx)
+    randaug = _batch_randaug(ctx)
     from .utils.metrics import StepProfiler
     prof = StepProfiler(int(os.environ.get("MX_PROFILE", "0") or 0) if epoch == 0 else 0, save_path,
                         ctx.rank)
@@ -200,6 +213,10 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             sb.begin()
         samples = samples.to(ctx.device, non_blocking=True)
         labels = labels.to(ctx.device, non_blocking=True)
+        if randaug is not None:
+            # the policy's n ops per sample come first, as a transform pipeline orders them; each
+            # slot runs out of place, so this may hand on its own persistent buffer (as the mixer's)
+            samples = randaug(samples, epoch, step)
         if jitter is not None:
             # photometric first, as a transform pipeline orders it: the erase writes the mean colour
             # (0) into a picture that already has its colours; in place, like the erase below
