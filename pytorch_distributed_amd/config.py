@@ -66,11 +66,15 @@ class RunConfig:
     opt: str = "sgd"                 # sgd | adamw | lamb
     betas: tuple = (0.9, 0.999)      # AdamW / LAMB moment decays b1, b2 in [0, 1)
     opt_eps: float = 1e-8            # AdamW / LAMB eps
+    loss: str = "ce"                 # training loss: ce (softmax) | bce (sigmoid on the same soft targets)
+    bce_target_thresh: Optional[float] = None   # bce: target = [q > thresh], thresh in [0, 1) (None = off)
+    bce_sum: bool = False            # bce: sum over the classes instead of their mean
 
     @property
     def soft_targets(self) -> bool:
-        """Label smoothing, mixup or CutMix is on: the loss takes soft targets."""
-        return self.label_smoothing > 0 or self.mixup > 0 or self.cutmix > 0
+        """Label smoothing, mixup or CutMix is on, or the loss is the sigmoid one: the training
+        criterion takes soft targets (and a captured step cannot run it)."""
+        return self.label_smoothing > 0 or self.mixup > 0 or self.cutmix > 0 or self.loss == "bce"
 
     def replace(self, **kw) -> "RunConfig":
         return dataclasses.replace(self, **kw)
@@ -161,6 +165,9 @@ _ENV = {
     "MX_BETAS": ("betas", _betas),
     "MX_OPT_EPS": ("opt_eps", float),
     "MX_WEIGHT_DECAY": ("weight_decay", float),
+    "MX_LOSS": ("loss", str),
+    "MX_BCE_TARGET_THRESH": ("bce_target_thresh", float),
+    "MX_BCE_SUM": ("bce_sum", _bool),
 }
 
 
@@ -232,6 +239,14 @@ def config_for(script: str, env: Optional[dict] = None,
     for var, v in (("MX_OPT_EPS", cfg.opt_eps), ("MX_WEIGHT_DECAY", cfg.weight_decay)):
         if not v >= 0 or v == float("inf"):
             raise ValueError(f"{var} is a finite number >= 0, got {v!r}")
+    if cfg.loss not in ("ce", "bce"):
+        raise ValueError(f"MX_LOSS must be ce|bce, got {cfg.loss!r}")
+    if cfg.bce_target_thresh is not None and not 0 <= cfg.bce_target_thresh < 1:
+        raise ValueError(f"MX_BCE_TARGET_THRESH is a target threshold in [0, 1) (unset = off), got "
+                         f"{cfg.bce_target_thresh!r}")
+    if cfg.loss != "bce" and (cfg.bce_target_thresh is not None or cfg.bce_sum):
+        raise ValueError(f"MX_BCE_TARGET_THRESH / MX_BCE_SUM belong to MX_LOSS=bce: drop them or "
+                         f"MX_LOSS={cfg.loss}")
     if cfg.opt != "sgd" and (cfg.nesterov or cfg.lars > 0):
         raise ValueError(f"MX_NESTEROV / MX_LARS belong to SGD: drop them or MX_OPT={cfg.opt}")
     if cfg.nesterov and not cfg.momentum > 0:

@@ -373,6 +373,20 @@ int pda_xent_soft(const float* logits, int B, int K, int ld_in, const long long*
 int pda_batch_mix(const void* x, void* out, int B, int S, int dt, int layout, int mode, float lam,
                   float oml, int y1, int y2, int x1, int x2, int grid_cap, hipStream_t st);
 
+// ------------------------------------------------------------------ bce.hip
+// Sigmoid cross-entropy of [B, K] f32 logits (row stride ld_in) against t_k = q_k, or [q_k > thresh]
+// when thresh >= 0 (any negative value: no threshold), q the soft target of pda_xent_soft.
+// mode 0: loss_rows[b] = mean_k l_k, dlog = dl * gscale * gdev[0] / (B*K); mode 1 (sum over the
+// classes): loss_rows[b] = sum_k l_k, dlog = dl * gscale * gdev[0] / B. loss (nullable) =
+// mean(loss_rows); dlog [B, ld_out] of dt, columns K..ld_out-1 written 0, untouched with want_grad
+// 0; gdev nullable. Returns -2 and launches nothing for B < 1, K < 1, ld_in < K, ld_out < K with a
+// non-null dlog, a mode other than 0 / 1, lam outside [0, 1], eps or a non-negative thresh outside
+// [0, 1), NaN, an unknown dt, or a null logits / labels / loss_rows (dlog with want_grad).
+int pda_bce_soft(const float* logits, int B, int K, int ld_in, const long long* labels,
+                 const long long* labels_b, float lam, float eps, float thresh, int mode,
+                 float* loss_rows, float* loss, void* dlog, int ld_out, float gscale,
+                 const float* gdev, int dt, int want_grad, hipStream_t st);
+
 // ------------------------------------------------------------------ erase.hip
 // Random-erasing boxes of a batch of B SxS images, one launch on stream st: boxes (device int32
 // [B][4], 4-byte aligned) row b = (y1, y2, x1, x2), half-open, all zeros when sample b is left alone.

@@ -7,6 +7,8 @@
   elsewhere.
 * :class:`SoftCrossEntropy` -- the criterion of the torch engine and the CPU; the native engine's
   is :class:`~pytorch_distributed_amd.models.native.NativeCrossEntropy` (``xent_soft``).
+* :class:`SoftBCE` -- the sigmoid loss on the same soft targets (``MX_LOSS=bce``, timm's
+  BinaryCrossEntropy of the LAMB recipe); the native engine's is ``NativeBCE`` (``csrc/bce.hip``).
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ from torch import nn
 import torch.nn.functional as F
 
 __all__ = ["MIXUP", "CUTMIX", "draw_mix", "BatchMixer", "SoftCrossEntropy", "soft_cross_entropy",
-           "mix_torch", "MIX_REFUSAL"]
+           "mix_torch", "MIX_REFUSAL", "SoftBCE", "soft_bce", "BCE_REFUSAL"]
 
 MIXUP, CUTMIX = 0, 1          # ops.native_ops MIX_MIXUP / MIX_CUTMIX
 _STREAM = 0x4D4958            # "MIX": keeps these draws apart from every other (seed, ...) stream
@@ -28,6 +30,10 @@ MIX_REFUSAL = ("{what} cannot run label smoothing, mixup or CutMix: captured ste
                "DataParallel replica graphs) bake their loss arguments in at capture and would train "
                "on hard labels. Run without MX_GRAPH / on one device (the single-GPU and DDP scripts "
                "work), or drop MX_LABEL_SMOOTHING / MX_MIXUP / MX_CUTMIX")
+BCE_REFUSAL = ("{what} cannot run MX_LOSS=bce: captured steps (MX_GRAPH=1, the DataParallel replica "
+               "graphs) bake their loss in at capture and would train on the softmax cross-entropy. "
+               "Run without MX_GRAPH / on one device (the single-GPU and DDP scripts work), or drop "
+               "MX_LOSS")
 
 
 def draw_mix(seed: int, rank: int, epoch: int, step: int, S: int, mixup_alpha: float,
@@ -145,3 +151,44 @@ class SoftCrossEntropy(nn.Module):
 
     def forward(self, logits, labels, labels_b=None, lam: float = 1.0):
         return soft_cross_entropy(logits, labels, labels_b, lam, self.label_smoothing)
+
+
+def check_bce_args(label_smoothing: float, target_thresh: Optional[float]) -> None:
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1), got {label_smoothing!r}")
+    if target_thresh is not None and not 0.0 <= target_thresh < 1.0:
+        raise ValueError(f"target_thresh must be None (off) or lie in [0, 1), got {target_thresh!r}")
+
+
+def soft_bce(logits, labels, labels_b=None, lam: float = 1.0, eps: float = 0.0,
+             thresh: Optional[float] = None, sum_classes: bool = False):
+    """Sigmoid cross-entropy against the soft target q_k = eps/K + (1-eps) * (lam*[k==labels] +
+    (1-lam)*[k==labels_b]), or against [q_k > thresh] with a threshold (timm's
+    BinaryCrossEntropy): the mean over every element, or with ``sum_classes`` the batch mean of
+    the rows' sums. Plain torch; ``csrc/bce.hip`` evaluates the same definition."""
+    K = logits.shape[1]
+    a = F.one_hot(labels, K).to(logits.dtype)
+    b = a if labels_b is None else F.one_hot(labels_b, K).to(logits.dtype)
+    q = eps / K + ((1.0 - eps) * lam) * a + ((1.0 - eps) * (1.0 - lam)) * b
+    t = q if thresh is None else (q > thresh).to(logits.dtype)
+    loss = F.binary_cross_entropy_with_logits(logits, t, reduction="none")
+    return loss.sum(1).mean() if sum_classes else loss.mean()
+
+
+class SoftBCE(nn.Module):
+    """:func:`soft_bce` as the training criterion of the torch engine and the CPU (``MX_LOSS=bce``);
+    the native engine's is :class:`~pytorch_distributed_amd.models.native.NativeBCE`."""
+
+    soft_targets = True      # forward takes (logits, labels, labels_b, lam): trainer.build_criterion
+
+    def __init__(self, label_smoothing: float = 0.0, target_thresh: Optional[float] = None,
+                 sum_classes: bool = False) -> None:
+        super().__init__()
+        check_bce_args(label_smoothing, target_thresh)
+        self.label_smoothing = float(label_smoothing)
+        self.target_thresh = None if target_thresh is None else float(target_thresh)
+        self.sum_classes = bool(sum_classes)
+
+    def forward(self, logits, labels, labels_b=None, lam: float = 1.0):
+        return soft_bce(logits, labels, labels_b, lam, self.label_smoothing, self.target_thresh,
+                        self.sum_classes)

@@ -40,11 +40,12 @@ from torch import nn
 from ..ops import ext
 from ..ops import native_ops as K
 from ..ops.native_ops import ConvGeom, Workspace
-from .native_train import (NativeAdamW, NativeCrossEntropy, NativeSGD, NativeTrainer,  # noqa: F401 (re-exported)
-                           _XentFn, _XentSoftFn)
+from .native_train import (NativeAdamW, NativeBCE, NativeCrossEntropy, NativeSGD,  # noqa: F401 (re-exported)
+                           NativeTrainer, _XentFn, _XentSoftFn)
 from .resnet import Bottleneck, ResNet
 
-__all__ = ["NativeResNet", "NativeSGD", "NativeAdamW", "NativeCrossEntropy", "NativeTrainer", "supports"]
+__all__ = ["NativeResNet", "NativeSGD", "NativeAdamW", "NativeCrossEntropy", "NativeBCE", "NativeTrainer",
+           "supports"]
 
 ALIGN = 64  # elements; keeps every segment 16-B aligned in the 16-bit shadow
 # DDP bucket boundaries (block boundaries of the flat gradient) are padded to multiples of
@@ -1201,7 +1202,15 @@ class NativeResNet(nn.Module):
             raise ValueError(f"make_optimizer: opt is sgd, adamw or lamb, got {opt!r}")
         return NativeAdamW(self, *args, lamb=opt == "lamb", **kw)
 
-    def make_criterion(self, label_smoothing: float = 0.0) -> "NativeCrossEntropy":
+    def make_criterion(self, label_smoothing: float = 0.0, loss: str = "ce",
+                       target_thresh: Optional[float] = None, sum_classes: bool = False):
+        """``loss="ce"`` (the default): :class:`NativeCrossEntropy`; ``"bce"``: :class:`NativeBCE`,
+        which alone takes ``target_thresh`` and ``sum_classes``."""
+        if loss == "bce":
+            return NativeBCE(self, label_smoothing, target_thresh, sum_classes)
+        if loss != "ce" or target_thresh is not None or sum_classes:
+            raise ValueError(f"make_criterion: loss is ce or bce (target_thresh and sum_classes "
+                             f"belong to bce), got {loss!r}, {target_thresh!r}, {sum_classes!r}")
         return NativeCrossEntropy(self, label_smoothing)
 
     def _apply(self, fn, recurse=True):  # .to()/.cuda()/.half() would break the flat views

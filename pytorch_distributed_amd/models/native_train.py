@@ -14,7 +14,7 @@ from ..ops import native_ops as K
 if TYPE_CHECKING:
     from .native import NativeResNet
 
-__all__ = ["NativeSGD", "NativeAdamW", "NativeCrossEntropy", "NativeTrainer"]
+__all__ = ["NativeSGD", "NativeAdamW", "NativeCrossEntropy", "NativeBCE", "NativeTrainer"]
 
 
 class _XentFn(torch.autograd.Function):
@@ -107,6 +107,69 @@ class NativeCrossEntropy(nn.Module):
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         K.xent_soft(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss,
                     labels_b=labels_b, lam=lam, eps=eps)
+        return loss
+
+
+class _BceSoftFn(torch.autograd.Function):
+    """:class:`_XentSoftFn` with the sigmoid loss (K.bce_soft); ``kw``: eps, thresh, sum_classes."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, labels_b, lam, kw, model: NativeResNet):
+        B = logits.shape[0]
+        loss_rows = torch.empty(B, dtype=torch.float32, device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        K.bce_soft(logits, labels, loss_rows, loss, labels_b=labels_b, lam=lam, **kw)
+        ctx.save_for_backward(logits, labels, *(() if labels_b is None else (labels_b,)))
+        ctx.model, ctx.lam, ctx.kw = model, lam, kw
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, *rest = ctx.saved_tensors
+        m: NativeResNet = ctx.model
+        B = logits.shape[0]
+        dlog16 = torch.empty(B, m.fc_rows, dtype=m.dtype, device=logits.device)
+        gdev = g.reshape(1).to(torch.float32).contiguous()
+        # (the kernel owns the reduction's 1/(B*K) or 1/B: gscale stays 1)
+        K.bce_soft(logits, labels, torch.empty(B, device=logits.device), None,
+                   labels_b=rest[0] if rest else None, lam=ctx.lam, dlog=dlog16, gdev=gdev, **ctx.kw)
+        m._pending_dlog16 = dlog16
+        return torch.empty_like(logits), None, None, None, None, None
+
+
+class NativeBCE(nn.Module):
+    """Sigmoid (binary) cross-entropy on the soft targets of :class:`NativeCrossEntropy`, fused
+    with its gradient kernel for the native engine (``csrc/bce.hip``): timm's BinaryCrossEntropy,
+    the loss LAMB's ResNet recipe trains with. ``target_thresh`` (None: off) turns the smoothed,
+    mixed target into [q > thresh]; ``sum_classes`` sums the classes instead of averaging them."""
+
+    soft_targets = True      # forward takes (logits, labels, labels_b, lam): trainer.build_criterion
+
+    def __init__(self, model: Optional[NativeResNet] = None, label_smoothing: float = 0.0,
+                 target_thresh: Optional[float] = None, sum_classes: bool = False) -> None:
+        super().__init__()
+        from ..mix import check_bce_args
+        check_bce_args(label_smoothing, target_thresh)
+        self.model = model
+        self.label_smoothing = float(label_smoothing)
+        self.target_thresh = None if target_thresh is None else float(target_thresh)
+        self.sum_classes = bool(sum_classes)
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor,
+                labels_b: Optional[torch.Tensor] = None, lam: float = 1.0) -> torch.Tensor:
+        m = self.model
+        lam = float(lam)
+        if m is None or not logits.is_cuda or logits.dtype != torch.float32:
+            from ..mix import soft_bce
+            return soft_bce(logits.float(), labels, labels_b, lam, self.label_smoothing,
+                            self.target_thresh, self.sum_classes)
+        kw = dict(eps=self.label_smoothing, thresh=self.target_thresh, sum_classes=self.sum_classes)
+        if logits.requires_grad:
+            return _BceSoftFn.apply(logits, labels, labels_b, lam, kw, m)
+        B = logits.shape[0]
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        K.bce_soft(logits.contiguous(), labels, torch.empty(B, device=logits.device), loss,
+                   labels_b=labels_b, lam=lam, **kw)
         return loss
 
 

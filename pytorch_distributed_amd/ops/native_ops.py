@@ -33,6 +33,7 @@ __all__ = [
     "FLAT_CHUNK", "SEG_CHUNK", "SegTables", "seg_tables", "seg_norms", "sgd_seg", "grad_clip",
     "ADAM_HYPER", "AdamTables", "adam_tables", "adam_tick", "adamw_seg", "lamb_moments", "lamb_apply",
     "xent_soft", "xent_soft_check", "batch_mix", "batch_mix_check", "mix_weights",
+    "bce_soft", "bce_soft_check",
     "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
     "jitter_strengths", "jitter_draw", "jitter_bps", "batch_jitter", "batch_jitter_check",
     "randaug_stat_row", "randaug_check", "randaug_draw", "randaug_bps", "randaug_stats", "randaug_apply",
@@ -1255,6 +1256,43 @@ def xent_soft(logits: torch.Tensor, labels: torch.Tensor, loss_rows, loss, label
                                  eps, ptr(loss_rows), ptr(loss), ptr(dlog), ld_out, float(gscale),
                                  ptr(gdev), dt, int(dlog is not None), stream(logits.device))
     check(rc, "xent_soft")
+
+
+def bce_soft_check(logits, labels, labels_b, lam: float, eps: float, thresh: Optional[float] = None,
+                   dlog=None) -> Tuple[int, int]:
+    """Host-side validation of a :func:`bce_soft` call; returns (B, K). :func:`xent_soft_check`'s
+    rules, and a threshold that is None (off) or lies in [0, 1)."""
+    try:
+        B, K = xent_soft_check(logits, labels, labels_b, lam, eps, dlog)
+    except ValueError as e:
+        raise ValueError(str(e).replace("xent_soft", "bce_soft")) from None
+    if thresh is not None and not 0.0 <= thresh < 1.0:
+        raise ValueError(f"bce_soft: thresh must be None (off) or lie in [0, 1), got {thresh!r}")
+    return B, K
+
+
+def bce_soft(logits: torch.Tensor, labels: torch.Tensor, loss_rows, loss, labels_b=None,
+             lam: float = 1.0, eps: float = 0.0, thresh: Optional[float] = None,
+             sum_classes: bool = False, dlog=None, gscale: float = 1.0,
+             gdev: Optional[torch.Tensor] = None) -> None:
+    """Sigmoid cross-entropy against :func:`xent_soft`'s soft target q, or against [q > thresh]
+    with a threshold (timm's BinaryCrossEntropy): l_k = max(z,0) - z*t_k + log1p(exp(-|z|)).
+    loss_rows = the mean of l_k over the classes (``sum_classes``: their sum), loss (nullable) =
+    mean(loss_rows), dlog ([B, ld] f32 / bf16 / f16, padding columns 0) = d(loss)/dz * gscale *
+    gdev[0], from one read of the logits in one launch (csrc/bce.hip). Arguments are validated on
+    the host first (:func:`bce_soft_check`)."""
+    if loss_rows is None:
+        raise ValueError("bce_soft: loss_rows is required (the kernel writes it on every launch)")
+    lam, eps = float(lam), float(eps)
+    thresh = None if thresh is None else float(thresh)
+    B, K = bce_soft_check(logits, labels, labels_b, lam, eps, thresh, dlog)
+    ld_out = dlog.shape[1] if dlog is not None else 0
+    dt = dt_of(dlog) if dlog is not None else 1
+    rc = ext.lib().pda_bce_soft(ptr(logits), B, K, logits.stride(0), ptr(labels), ptr(labels_b), lam,
+                                eps, -1.0 if thresh is None else thresh, int(bool(sum_classes)),
+                                ptr(loss_rows), ptr(loss), ptr(dlog), ld_out, float(gscale),
+                                ptr(gdev), dt, int(dlog is not None), stream(logits.device))
+    check(rc, "bce_soft")
 
 
 def topk_hits(logits, labels, hits) -> None:

@@ -205,10 +205,16 @@ class DataParallel(nn.Module):
         kw.pop("lars", None), kw.pop("lars_eps", None)
         return torch.optim.SGD(params, **kw)
 
-    def make_criterion(self, label_smoothing: float = 0.0):
+    def make_criterion(self, label_smoothing: float = 0.0, loss: str = "ce", **bce):
         if not self.replicas and hasattr(self.module, "make_criterion"):
-            return self.module.make_criterion(label_smoothing)
+            return self.module.make_criterion(label_smoothing, loss=loss, **bce)
         # gathered logits: gradient flows back through _Gather
+        if loss == "bce":
+            from ..mix import SoftBCE
+            return SoftBCE(label_smoothing, **bce)
+        if loss != "ce" or bce:
+            raise ValueError(f"make_criterion: loss is ce or bce (target_thresh and sum_classes "
+                             f"belong to bce), got {loss!r}, {bce!r}")
         if label_smoothing > 0:
             from ..mix import SoftCrossEntropy
             return SoftCrossEntropy(label_smoothing)

@@ -478,22 +478,32 @@ def _refuse_soft_targets(cfg: RunConfig, model: nn.Module, ctx: Context) -> None
     several devices refuse label smoothing / mixup / CutMix (ValueError, before training starts)."""
     if not cfg.soft_targets:
         return
-    from .mix import MIX_REFUSAL
+    from .mix import BCE_REFUSAL, MIX_REFUSAL
+    refusal = BCE_REFUSAL if cfg.loss == "bce" else MIX_REFUSAL
     if cfg.graph and ctx.engine == "native":
-        raise ValueError(MIX_REFUSAL.format(what="MX_GRAPH=1"))
+        raise ValueError(refusal.format(what="MX_GRAPH=1"))
     from .runtime.graphs import DP_REPLAY, replays_captured_steps
     if replays_captured_steps(model):
-        raise ValueError(MIX_REFUSAL.format(what=DP_REPLAY))
+        raise ValueError(refusal.format(what=DP_REPLAY))
 
 
-def build_criterion(ctx: Context, model: nn.Module):
+def build_criterion(ctx: Context, model: nn.Module, train: bool = True):
     """The loss: the native engine's fused kernel, else ``nn.CrossEntropyLoss``. With
     ``MX_LABEL_SMOOTHING`` / ``MX_MIXUP`` / ``MX_CUTMIX`` the criterion takes ``(outputs, labels,
     labels_b, lam)``: the native one with the smoothing passed through, on the torch engine and
-    the CPU :class:`~pytorch_distributed_amd.mix.SoftCrossEntropy`."""
+    the CPU :class:`~pytorch_distributed_amd.mix.SoftCrossEntropy`. ``MX_LOSS=bce`` makes the
+    training criterion the sigmoid loss on the same targets (the native engine's ``NativeBCE``,
+    else :class:`~pytorch_distributed_amd.mix.SoftBCE`); ``train=False`` is the validation
+    criterion, which stays the softmax cross-entropy (as timm validates)."""
     cfg = ctx.cfg
     _refuse_soft_targets(cfg, model, ctx)
     inner = _factory_owner(model, "make_criterion")
+    if cfg.loss == "bce" and train:
+        bce = dict(target_thresh=cfg.bce_target_thresh, sum_classes=cfg.bce_sum)
+        if hasattr(inner, "make_criterion"):
+            return inner.make_criterion(label_smoothing=cfg.label_smoothing, loss="bce", **bce)
+        from .mix import SoftBCE
+        return SoftBCE(cfg.label_smoothing, **bce)
     if hasattr(inner, "make_criterion"):
         if cfg.label_smoothing > 0:
             crit = inner.make_criterion(label_smoothing=cfg.label_smoothing)
@@ -545,6 +555,8 @@ def run(cfg: RunConfig, mode: str, local_rank: int = 0, nprocs: Optional[int] = 
     per_rank_batch = cfg.batch_size
     train_loader, val_loader, train_sampler = _make_loaders(cfg, ctx, model, per_rank_batch)
     criterion = build_criterion(ctx, model)
+    # MX_LOSS=bce trains on the sigmoid loss and validates on the softmax cross-entropy
+    val_criterion = criterion if cfg.loss == "ce" else build_criterion(ctx, model, train=False)
     optimizer = build_optimizer(cfg, model, ctx)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=cfg.lr_step, gamma=cfg.lr_gamma)
     if mode == "ddp_amp":
@@ -593,14 +605,14 @@ def run(cfg: RunConfig, mode: str, local_rank: int = 0, nprocs: Optional[int] = 
             util, util_method = sbusy.overall(), "step intervals (HIP events) / wall time"
         start_step = 0
         scheduler.step()
-        acc = validate(val_loader, model, criterion, epoch, ctx)
+        acc = validate(val_loader, model, val_criterion, epoch, ctx)
         # MX_EMA: a second pass over the averaged weights, which then decide (and are) best.pt
         with ema.swapped() if ema is not None else contextlib.nullcontext():
             more = {}
             if cfg.clip_grad_norm > 0 and ctx.extra.get("grad_norm") is not None:
                 more["grad_norm"] = float(ctx.extra["grad_norm"])
             if ema is not None:
-                more["ema_acc1"] = validate(val_loader, model, criterion, epoch, ctx, prefix="EMA ")
+                more["ema_acc1"] = validate(val_loader, model, val_criterion, epoch, ctx, prefix="EMA ")
             t2 = time.time()
             if cfg.empty_cache == "epoch" and device.type == "cuda":
                 torch.cuda.empty_cache()
