@@ -27,7 +27,7 @@ ARCH = os.environ.get("PDA_ARCH", "gfx950")
 
 KERNEL_SRCS = ["conv_gemm.hip", "bn.hip", "misc.hip", "stem.hip", "wgrad_tap.hip", "augment.hip",
                "optim.hip", "mix.hip", "ema.hip", "clip.hip", "erase.hip", "adam.hip", "jitter.hip",
-               "randaug.hip", "bce.hip"]
+               "randaug.hip", "bce.hip", "threeaug.hip"]
 COMM_SRCS = ["comm/rccl_comm.cpp", "comm/reducer.cpp"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"]
 
@@ -49,10 +49,13 @@ def _newer(src: Path, obj: Path, deps) -> bool:
 # adam.hip writes its fused operations as fmaf and keeps the rest apart (both LAMB phases must
 # form the same bits of u); it is also built without packed-f32 instructions (v_pk_*_f32, 96 of them
 # otherwise): scalar VALU forms only, at 77 / 64 VGPRs for adamw_seg / lamb_apply instead of 88 / 86;
-# bce.hip forms its targets and loss terms as the sums and products its float64 reference writes
+# bce.hip forms its targets and loss terms as the sums and products its float64 reference writes;
+# threeaug.hip as jitter.hip: its draw mirrors threeaug.py draw_three_aug, its blur sums are the
+# fmaf chains the source writes and nothing else is fused
 FILE_FLAGS = {"conv_gemm.hip": ["-fno-slp-vectorize"], "augment.hip": ["-ffp-contract=off"],
               "erase.hip": ["-ffp-contract=off"], "jitter.hip": ["-ffp-contract=off"],
               "randaug.hip": ["-ffp-contract=off"], "bce.hip": ["-ffp-contract=off"],
+              "threeaug.hip": ["-ffp-contract=off"],
               "adam.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang",
                            "-packed-fp32-ops"]}
 

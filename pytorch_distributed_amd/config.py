@@ -63,6 +63,7 @@ class RunConfig:
     random_erase: float = 0.0        # random-erasing probability p in [0, 1] (0 = off)
     color_jitter: tuple = (0.0, 0.0, 0.0, 0.0)   # ColorJitter strengths (brightness, contrast, saturation, hue)
     rand_augment: tuple = (0, 0)     # RandAugment (n ops in 0..4, magnitude bin m in 0..30); n = 0: off
+    three_augment: bool = False      # DeiT-III's 3-Augment: one of grayscale / solarize / Gaussian blur per sample
     opt: str = "sgd"                 # sgd | adamw | lamb
     betas: tuple = (0.9, 0.999)      # AdamW / LAMB moment decays b1, b2 in [0, 1)
     opt_eps: float = 1e-8            # AdamW / LAMB eps
@@ -122,6 +123,12 @@ def _rand_augment(s: str) -> tuple:
     return v
 
 
+def _three_augment(s: str) -> bool:
+    if s not in ("0", "1"):
+        raise ValueError(f"MX_THREE_AUGMENT is 0|1, got {s!r}")
+    return s == "1"
+
+
 _ENV = {
     "MX_EPOCHS": ("epochs", int),
     "MX_BATCH": ("batch_size", int),
@@ -161,6 +168,7 @@ _ENV = {
     "MX_RANDOM_ERASE": ("random_erase", float),
     "MX_COLOR_JITTER": ("color_jitter", _color_jitter),
     "MX_RAND_AUGMENT": ("rand_augment", _rand_augment),
+    "MX_THREE_AUGMENT": ("three_augment", _three_augment),
     "MX_OPT": ("opt", str),
     "MX_BETAS": ("betas", _betas),
     "MX_OPT_EPS": ("opt_eps", float),

@@ -469,6 +469,23 @@ int pda_randaug_apply(const void* src, void* dst, const int* table, int n, int s
                       long long stats_len, const double* slab, long long slab_len, int B, int S, int dt,
                       int layout, const float* mean, const float* stdev, int grid_cap, hipStream_t st);
 
+// ------------------------------------------------------------------ threeaug.hip
+// 3-Augment table of a batch of B samples, one launch on stream st: table (device int32 [B][16],
+// 4-byte aligned) row n = (op, the bits of the float32 sigma, R, 0, the bits of the float32 blur
+// weights w[0] .. w[11], 0 beyond R); op 0 grayscale, 1 solarize, 2 Gaussian blur of radius R.
+// bkey: the batch's key (threeaug.py batch_key). Returns -2 and launches nothing for B <= 0, R
+// outside 1..11, or a null or misaligned table.
+int pda_three_aug_draw(int B, int R, unsigned bkey, int* table, hipStream_t st);
+// dst = normalise(op(clamp(src * stdev + mean, 0, 1))) with the op of each sample's table row, one
+// launch; the blur is separable over 2 R + 1 taps per axis with reflect padding (no edge repeat),
+// the horizontal pass first, from the row's weights alone (those beyond R count as 0; sigma is not
+// read). x, layouts, dtypes and grid_cap as pda_batch_erase; the s2d padding slots of dst get src's
+// bits. The rows' VALUES are the caller's to check (op in 0..2, R in 1..11 and below S): the kernel
+// stays inside its buffers for any row, but defines no result for a bad one. Returns -2 for what
+// pda_batch_erase refuses, src and dst that overlap, or a null or misaligned table.
+int pda_three_aug(const void* src, void* dst, const int* table, int B, int S, int dt, int layout,
+                  const float* mean, const float* stdev, int grid_cap, hipStream_t st);
+
 // ------------------------------------------------------------------ ema.hip
 // Host-side validation of a range table. 0 = good; otherwise the negative code that
 // ops/native_ops.py turns into a ValueError:

@@ -37,6 +37,7 @@ __all__ = [
     "erase_draw", "erase_bounds", "batch_erase", "batch_erase_check",
     "jitter_strengths", "jitter_draw", "jitter_bps", "batch_jitter", "batch_jitter_check",
     "randaug_stat_row", "randaug_check", "randaug_draw", "randaug_bps", "randaug_stats", "randaug_apply",
+    "THREE_AUG_RMAX", "three_aug_check", "three_aug_draw", "three_aug",
 ]
 
 
@@ -2192,6 +2193,90 @@ def randaug_apply(src, dst, table, slot: int, stats, slab, layout: int, grid_cap
     check(ext.lib().pda_randaug_apply(ptr(src), ptr(dst), ptr(table), n, int(slot), ptr(stats), stats.numel(),
                                       ptr(slab), slab.numel(), B, S, dt_of(src), layout, mean, std, grid_cap,
                                       stream(src.device)), "randaug_apply")
+
+
+# ------------------------------------------------------------------ 3-Augment of a batch
+THREE_AUG_RMAX = 11                # csrc/threeaug.hip RMAX: the blur's largest radius (23 taps per axis)
+
+
+def _three_aug_table(what: str, table, B: Optional[int] = None) -> int:
+    if (table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 16 or not table.is_contiguous()
+            or table.shape[0] < 1 or (B is not None and table.shape[0] != B)):
+        raise ValueError(f"{what}: the table must be a contiguous int32 [B, 16] tensor of "
+                         f"{B if B is not None else '>= 1'} rows, got {tuple(table.shape)} {table.dtype}")
+    return table.shape[0]
+
+
+def three_aug_check(src, dst, table, layout: int, rows=None) -> Tuple[int, int]:
+    """Host-side validation of a :func:`three_aug` call; returns (B, S). Pure Python (the kernel
+    library is not loaded), run before the launch. ``rows``: the table's values on the host (an
+    int array [B, 16]), each row held to op in 0..2 and a radius R in 1..``THREE_AUG_RMAX`` below the
+    image side (the reflection of an R-wide border needs R <= S - 1); None: the values are the
+    caller's word (``max_r`` of :func:`three_aug`)."""
+    B, S = batch_shape("three_aug", src, layout)
+    _three_aug_table("three_aug", table, B)
+    if table.device != src.device:
+        raise ValueError(f"three_aug: the table must be on the batch's {src.device}")
+    if (dst.shape != src.shape or dst.dtype != src.dtype or dst.device != src.device
+            or not dst.is_contiguous() or dst.data_ptr() % 16):
+        raise ValueError(f"three_aug: dst must be contiguous, 16-byte aligned and have the shape, dtype "
+                         f"and device of src, got {tuple(dst.shape)} {dst.dtype} {dst.device}")
+    nbytes = src.numel() * src.element_size()
+    if src.data_ptr() < dst.data_ptr() + nbytes and dst.data_ptr() < src.data_ptr() + nbytes:
+        raise ValueError("three_aug: dst overlaps src (the blur reads a neighbourhood: it runs out of place)")
+    if rows is not None:
+        for b, r in enumerate(rows):
+            op, R = int(r[0]), int(r[2])
+            if op not in (0, 1, 2):
+                raise ValueError(f"three_aug: sample {b}: op {op} is none of 0 grayscale, 1 solarize, 2 blur")
+            if not 1 <= R <= THREE_AUG_RMAX or R >= S:
+                raise ValueError(f"three_aug: sample {b}: radius {R} outside 1..{THREE_AUG_RMAX} or not below "
+                                 f"the image side {S}")
+    return B, S
+
+
+def three_aug_draw(table, bkey: int, R: int = THREE_AUG_RMAX) -> None:
+    """Draw the 3-Augment table of a batch on the device (one launch, csrc/threeaug.hip
+    ``three_aug_draw_kernel``) into ``table``, a device int32 [B, 16] tensor (``threeaug.three_aug_table``'s
+    packing): per sample one of grayscale / solarize / blur, the blur's sigma in [0.1, 2] and its
+    ``R + 1`` float32 weights. ``bkey``: ``threeaug.batch_key(seed, rank, epoch, step)``;
+    ``threeaug.draw_three_aug`` is the host mirror."""
+    B = _three_aug_table("three_aug_draw", table)
+    if int(R) != R or not 1 <= R <= THREE_AUG_RMAX:
+        raise ValueError(f"three_aug_draw: the radius {R!r} lies outside 1..{THREE_AUG_RMAX}")
+    if table.device.type != "cuda":
+        raise ValueError("three_aug_draw runs on a GPU; the table is on " + str(table.device))
+    if table.data_ptr() % 4:
+        raise ValueError("three_aug_draw: the table must be 4-byte aligned")
+    check(ext.lib().pda_three_aug_draw(B, int(R), int(bkey) & 0xFFFFFFFF, ptr(table), stream(table.device)),
+          "three_aug_draw")
+
+
+def three_aug(src, dst, table, layout: int, grid_cap: int = 0, max_r: Optional[int] = None) -> None:
+    """``dst`` = the op of every sample's ``table`` row (device int32 [B, 16], as :func:`three_aug_draw`
+    writes it) applied to ``src``, one launch (csrc/threeaug.hip): grayscale, solarize at 128 / 255, or
+    the separable Gaussian blur with the row's weights through LDS tiles, between un-normalising and
+    re-normalising with ``data/synthetic.py``'s MEAN and STD. ``layout``: ``AUG_S2D`` [B, S/2, S/2, 16]
+    (f32 / bf16 / f16) or ``AUG_NCHW`` [B, 3, S, S] f32. Out of place; the s2d padding slots of ``dst``
+    get ``src``'s. ``max_r``: the radius every row was drawn with, when the caller drew the table
+    itself (checked against S; the rows are then not read back: no host sync); None: the table is
+    copied to the host and every row checked (:func:`three_aug_check`)."""
+    from ..data.synthetic import MEAN, STD
+    rows = None
+    if max_r is None:
+        _three_aug_table("three_aug", table)
+        rows = table.cpu().numpy()
+    B, S = three_aug_check(src, dst, table, layout, rows)
+    if max_r is not None and (int(max_r) != max_r or not 1 <= max_r <= THREE_AUG_RMAX or max_r >= S):
+        raise ValueError(f"three_aug: radius {max_r!r} outside 1..{THREE_AUG_RMAX} or not below the image "
+                         f"side {S}")
+    if src.device.type != "cuda":
+        raise ValueError("three_aug runs on a GPU; the batch is on " + str(src.device))
+    if src.data_ptr() % 16 or table.data_ptr() % 4:
+        raise ValueError("three_aug: src must be 16-byte aligned (the table 4-byte)")
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    check(ext.lib().pda_three_aug(ptr(src), ptr(dst), ptr(table), B, S, dt_of(src), layout, mean, std, grid_cap,
+                                  stream(src.device)), "three_aug")
 
 
 AUG_TRAIN, AUG_VAL = 0, 1

@@ -181,6 +181,18 @@ def _batch_randaug(ctx: Context):
     return randaug
 
 
+def _batch_three_aug(ctx: Context):
+    """``MX_THREE_AUGMENT``: the run's :class:`~pytorch_distributed_amd.threeaug.BatchThreeAugment`
+    (kept on the context: its table and second buffer serve every epoch), else None."""
+    if not ctx.cfg.three_augment:
+        return None
+    three = ctx.extra.get("three_aug")
+    if three is None:
+        from .threeaug import BatchThreeAugment
+        three = ctx.extra["three_aug"] = BatchThreeAugment(ctx.cfg, ctx)
+    return three
+
+
 def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: Context,
           start_step: int, best_acc: float, save_path: Path) -> int:
     """One epoch of training (reference ``restnet_ddp.py:19-47``). Returns steps run."""
@@ -193,6 +205,7 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
     eraser = _batch_eraser(ctx)
     jitter = _batch_jitter(ctx)
     randaug = _batch_randaug(ctx)
+    three_aug = _batch_three_aug(ctx)
     from .utils.metrics import StepProfiler
     prof = StepProfiler(int(os.environ.get("MX_PROFILE", "0") or 0) if epoch == 0 else 0, save_path,
                         ctx.rank)
@@ -217,6 +230,10 @@ def train(dataloader, model, criterion, optimizer, scheduler, epoch: int, ctx: C
             # the policy's n ops per sample come first, as a transform pipeline orders them; each
             # slot runs out of place, so this may hand on its own persistent buffer (as the mixer's)
             samples = randaug(samples, epoch, step)
+        if three_aug is not None:
+            # timm's order: the policy, then one of grayscale / solarize / blur, then the colour
+            # jitter; out of place (the blur reads a neighbourhood): hands on its persistent buffer
+            samples = three_aug(samples, epoch, step)
         if jitter is not None:
             # photometric first, as a transform pipeline orders it: the erase writes the mean colour
             # (0) into a picture that already has its colours; in place, like the erase below
